@@ -6,7 +6,12 @@ in HBM: FNV-1a key hashes + FNV-1 fingerprints, every BBHash level, level ranks,
 the mph_fp / mph_pos placement — the work of StreamingMPHFBuilder.Build minus file
 I/O (/root/reference/pkg/format/mphf_streaming.go:122-213).
 
-  python bench.py [--gpus N --steps K --warmup W --config c3]
+  python bench.py [--gpus N --steps K --warmup W --config c3] [--full] [--dump-outputs DIR]
+  A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+  `ms_per_step`, ...).  --full adds everything measured beside the headline: the profiled
+  pass (`stages_ms`, `roofline`), lookup / finalize / host_e2e, `bitmap_n1`, the C2 / C5
+  lines and the CPU baselines (each can be dropped again with its --no-* switch).
+  --dump-outputs DIR writes what the last timed step produced as DIR/<name>.npy.
   N > 1: torchrun --nproc-per-node N bench.py --gpus N ...  (one process per GPU;
          RCCL communicator owned by libs3imph; torch.distributed/gloo only for the
          rendezvous, barriers and the max-over-ranks time).  `python bench.py --gpus N`
@@ -15,8 +20,8 @@ I/O (/root/reference/pkg/format/mphf_streaming.go:122-213).
 
 Workload: BASELINE.json configs[2] (C3), the largest single-GPU configuration:
 100M synthetic prefixes per GPU, avg key 64 B (weak scaling: N GPUs build one MPHF over
-N x 100M keys).  At N = 1 lines ride beside it (never `value`): C2 (configs[1], 10M keys,
-avg 32 B) as `secondary.c2`, the C5 share of one GPU (25M keys, 1-1024 B) as
+N x 100M keys).  With --full at N = 1 lines ride beside it (never `value`): C2
+(configs[1], 10M keys, avg 32 B) as `secondary.c2`, the C5 share of one GPU (25M keys, 1-1024 B) as
 `secondary.c5`, and C3 through the north_star's per-level collision-bitmap decomposition
 at one rank as `bitmap_n1`.
 """
@@ -79,7 +84,13 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything that rides beside the headline: the profiled pass (stages_ms, "
+                         "roofline), lookup / finalize / host_e2e, bitmap_n1, the C2 / C5 lines, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (mph_fp, mph_pos, "
+                         "mph.bin; seeded samples plus whole-array digests) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--dist", action="store_true", help="use the multi-GPU build path even at N=1")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "host"],
                     help="N>1 collectives: RCCL over xGMI (default), or host copies over gloo — a rehearsal "
@@ -91,9 +102,10 @@ def main() -> None:
     ap.add_argument("--alt", action="store_true",
                     help="N > 1: also time the other decomposition on the same shards (alt_decomposition); "
                          "off by default, so the scaling line depends on the timed decomposition alone")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C2 line beside the C3 headline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full without the C2 / C5 / bitmap_n1 lines beside the C3 headline")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the lookup / finalize / host_e2e lines (profiling runs)")
+                    help="--full without the lookup / finalize / host_e2e lines (profiling runs)")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="rocprofv3 PMC summary (HBM bytes per launch) to attach as roofline.traffic")
     ap.add_argument("--probe-launch", action="store_true",
@@ -171,8 +183,12 @@ def main() -> None:
         def step():
             return ctx.build(d_blob, d_offs, n, d_fp, d_po)
     else:
+        last_shard = {}  # this rank's output count and segments of the last build (--dump-outputs)
+
         def step():
-            return ctx.build_shard(d_blob, d_offs, n, plan.lo, d_fp, d_po, out_cap)[2]
+            last_shard["count"], last_shard["segments"], step_info = ctx.build_shard(
+                d_blob, d_offs, n, plan.lo, d_fp, d_po, out_cap)
+            return step_info
 
     bitmap_error = None
     if use_dist and args.decomp == "bitmap":
@@ -216,13 +232,23 @@ def main() -> None:
     barrier()
     t1 = time.perf_counter()
     timed_stages = {k: v / args.steps for k, v in stage_sum.items()}
-    ctx.set_profiling(1)
-    prof_steps = min(args.steps, 5)
-    stage_sum = {}
-    for _ in range(prof_steps):
-        step()
-        for k, v in ctx.stage_times().items():
-            stage_sum[k] = stage_sum.get(k, 0.0) + v
+    if args.dump_outputs:
+        # what the last timed step left in the caller's arrays, before anything builds again
+        if use_dist:
+            dump_outputs(args.dump_outputs, d_fp, d_po, last_shard["count"], ctx.mph_bin(),
+                         suffix=f"_rank{rank}" if world > 1 else "", segments=last_shard["segments"])
+        else:
+            dump_outputs(args.dump_outputs, d_fp, d_po, n, ctx.mph_bin())
+    stages = {}
+    if args.full:
+        ctx.set_profiling(1)
+        prof_steps = min(args.steps, 5)
+        stage_sum = {}
+        for _ in range(prof_steps):
+            step()
+            for k, v in ctx.stage_times().items():
+                stage_sum[k] = stage_sum.get(k, 0.0) + v
+        stages = {k: v / prof_steps for k, v in stage_sum.items()}
     ctx.set_profiling(0)
     dt = (t1 - t0) / args.steps
     if dist is not None:
@@ -235,7 +261,6 @@ def main() -> None:
     else:
         key_bytes = key_bytes_local
     n_global = plan.n_global
-    stages = {k: v / prof_steps for k, v in stage_sum.items()}
     # The other decomposition of the sharded levels, timed the same way on the same keys
     # (N > 1 with --alt; beside `value`, never as it).  Off by default: the routed build has
     # never run over RCCL at N > 1, and a line must not depend on it.
@@ -272,7 +297,6 @@ def main() -> None:
                    "key_bytes": key_bytes, "parallelism": f"shard{world}" if use_dist else "single",
                    "gamma": 2.0, "levels": info.get("num_levels")},
         "key_bytes_GBps": key_bytes / dt / 1e9,
-        "stages_ms": {k: round(v, 4) for k, v in stages.items()},  # profiled pass after the timed loop
         "pipeline_roofline": {"bound": "hbm", "alg_bytes": b_alg, "achieved": b_alg / dt / 1e9,
                               "peak": HBM_PEAK_GBPS * world, "unit": "GB/s",
                               "frac": b_alg / dt / 1e9 / (HBM_PEAK_GBPS * world)},
@@ -287,7 +311,10 @@ def main() -> None:
         result["transport_fallback"] = fallback
     if bitmap_error is not None:
         result["bitmap_error"] = bitmap_error
-    # Roofline of the dominant kernel (rank 0's stage times, HIP events on the build stream).
+    if args.full:
+        result["stages_ms"] = {k: round(v, 4) for k, v in stages.items()}  # profiled pass after the timed loop
+    # Roofline of the dominant kernel (rank 0's stage times, HIP events on the build stream;
+    # --full: it is chosen from the profiled pass).
     dom = max((k for k in stages if stage_alg_bytes(k, n, key_bytes_local, info) is not None),
               key=lambda k: stages[k], default=None)
     if dom is not None:
@@ -330,21 +357,21 @@ def main() -> None:
     if alt is not None:
         result["alt_decomposition"] = {**alt, "keys_per_s": n_global / alt["ms_per_step"] * 1e3
                                        if alt.get("ms_per_step") else None}
-    if world == 1 and not use_dist and not args.headline_only:
+    if args.full and world == 1 and not use_dist and not args.headline_only:
         result["lookup"] = lookup_rate(ctx, d_blob, d_offs, n, d_fp, d_po)
         result["finalize"] = finalize_rate(ctx, d_blob, d_offs, n)
-    if world == 1 and not use_dist and not args.no_secondary:
+    if args.full and world == 1 and not use_dist and not args.no_secondary:
         # the north_star decomposition on the same keys at one rank (RCCL communicator of one)
         ctx.close()
         del d_fp, d_po
         torch.cuda.empty_cache()
         result["bitmap_n1"] = bitmap_n1_line(s3imph, torch, d_blob, d_offs, n, key_bytes_local, local_rank,
                                              args.steps, args.warmup)
-    if world == 1 and not args.headline_only:
+    if args.full and world == 1 and not args.headline_only:
         result["host_e2e"] = host_e2e(s3imph, blob, offs, local_rank)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(s3imph, cfg, args.seed)
-    if world == 1 and not use_dist and not args.no_secondary:
+    if args.full and world == 1 and not use_dist and not args.no_secondary:
         del d_blob, d_offs
         ctx.close()
         torch.cuda.empty_cache()
@@ -358,6 +385,64 @@ def main() -> None:
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20  # entries kept per dumped array (6 arrays of float64: 48 MiB at most)
+DUMP_SEED = 0x5EED
+
+
+def _limbs16(v: int, limbs: int = 4) -> list[float]:
+    """A non-negative integer as 16-bit limbs, least significant first (exact in float64)."""
+    return [float((v >> (16 * i)) & 0xFFFF) for i in range(limbs)]
+
+
+def dump_outputs(out_dir: str, d_fp, d_po, count: int, mph: bytes, suffix: str = "", segments=None) -> None:
+    """--dump-outputs: the arrays a caller of the timed build receives — mph_fp and mph_pos
+    (the first `count` entries of the device arrays) and mph.bin — as float64 .npy files
+    that hold every value exactly, so two builds can be compared entry for entry:
+
+      sample_index   the entries kept: all of them up to DUMP_SAMPLE, else a sorted sample
+                     drawn with a fixed seed (the same for every run with the same arguments)
+      mph_fp_hi32, mph_fp_lo32   the sampled fingerprints, upper and lower 32 bits
+      mph_pos        the sampled positions (below 2^53)
+      mph_bin_words  mph.bin as little-endian u32 words (zero-padded), sampled the same way
+      mph_bin_index  the word indices kept
+      digest         16-bit limbs of: sum(mph_fp) mod 2^64, sum(mph_pos) mod 2^64,
+                     crc32(mph.bin), len(mph.bin), count — over the whole arrays
+      segments       (sharded build) rows (global position, count, local offset)
+    `suffix` tells the ranks of an N > 1 run apart."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def pick(total: int) -> np.ndarray:
+        if total <= DUMP_SAMPLE:
+            return np.arange(total, dtype=np.int64)
+        return np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+
+    def save(name: str, a) -> None:
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.asarray(a, np.float64))
+
+    idx = pick(count)
+    d_idx = torch.from_numpy(idx).to(d_fp.device)
+    fp = d_fp[:count][d_idx].cpu().numpy().view(np.uint64)
+    po = d_po[:count][d_idx].cpu().numpy().view(np.uint64)
+    # int64 sums wrap, so they are the sums mod 2^64
+    fp_sum = int(d_fp[:count].sum().item()) & (2**64 - 1)
+    po_sum = int(d_po[:count].sum().item()) & (2**64 - 1)
+    save("sample_index", idx)
+    save("mph_fp_hi32", fp >> np.uint64(32))
+    save("mph_fp_lo32", fp & np.uint64(0xFFFFFFFF))
+    save("mph_pos", po)
+    words = np.frombuffer(mph + b"\0" * (-len(mph) % 4), dtype="<u4")
+    widx = pick(len(words))
+    save("mph_bin_index", widx)
+    save("mph_bin_words", words[widx])
+    save("digest", _limbs16(fp_sum) + _limbs16(po_sum) + _limbs16(zlib.crc32(mph), 2) + _limbs16(len(mph))
+         + _limbs16(count))
+    if segments is not None:
+        save("segments", np.asarray(segments, np.uint64).reshape(-1, 3))
 
 
 def launch_ranks(n: int, argv: list[str]) -> int:

@@ -35,7 +35,7 @@ TAG=$1; STEP=$2; shift 2
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
-short="--steps 5 --warmup 2 --no-cpu-baseline --no-secondary --headline-only"
+short="--full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --headline-only"
 stop() {  # a GPU fault, abort, segfault or time limit ends the whole call
   case $1 in 124|134|137|139) echo "$STEP stopped rc $1" >> "$OUT/status"; exit "$1";; esac
   return 0
@@ -64,7 +64,7 @@ case $STEP in
     [ -f "$OUT/pmc_traffic.json" ] || cp profiles/pmc_traffic.json "$OUT/pmc_traffic.json"
     for ctr in FETCH_SIZE WRITE_SIZE; do
       timeout -s KILL 150 rocprofv3 --pmc $ctr --output-format csv -d "$OUT/pmc_${ctr}_$NAME" -o run -- \
-        python3 bench.py --config "$CFG" --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --headline-only \
+        python3 bench.py --config "$CFG" --full --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --headline-only \
         "$@" $BENCH_EXTRA > "$OUT/pmc_${ctr}_$NAME.log" 2>&1
       rc=$?; stop $rc
       [ $rc = 0 ] || exit $rc
@@ -76,7 +76,7 @@ case $STEP in
   ctr)
     NAME=$1; CTRS=$2; shift 2
     timeout -s KILL 150 rocprofv3 --pmc $CTRS --output-format csv -d "$OUT/$NAME" -o run -- \
-      python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --headline-only "$@" $BENCH_EXTRA \
+      python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --headline-only "$@" $BENCH_EXTRA \
       > "$OUT/$NAME.log" 2>&1
     rc=$?; echo "ctr $NAME rc $rc" >> "$OUT/status"; exit $rc ;;
   ab)
@@ -85,7 +85,7 @@ case $STEP in
       i=0
       for e in "$@"; do
         i=$((i+1)); envs="S3IMPH_DEV=1"; [ "$e" != "-" ] && envs="$envs $e"
-        env $envs timeout -k 10 200 python bench.py --no-cpu-baseline --headline-only --no-secondary --config "$CFG" \
+        env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline --headline-only --no-secondary --config "$CFG" \
           --steps 20 $BENCH_EXTRA >> "$OUT/ab_v$i.log" 2>&1
         rc=$?; echo "ab v$i ($e) rep $rep rc $rc" >> "$OUT/status"; stop $rc
       done
@@ -97,7 +97,7 @@ case $STEP in
     for rep in $(seq "$REPS"); do
       for v in old new; do
         cp "abx/libs3imph_$v.so" $L
-        timeout -k 10 200 python bench.py --no-cpu-baseline --headline-only --no-secondary --config "$CFG" --steps 20 \
+        timeout -k 10 200 python bench.py --full --no-cpu-baseline --headline-only --no-secondary --config "$CFG" --steps 20 \
           $BENCH_EXTRA >> "$OUT/lib_${CFG}_$v.log" 2>&1
         rc=$?; echo "lib $v rep $rep rc $rc" >> "$OUT/status"; stop $rc
       done

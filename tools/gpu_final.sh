@@ -6,7 +6,7 @@
 #   bash tools/gpu_final.sh TAG
 T=${1:-final}
 bash tools/gpu.sh $T pytest &&
-bash tools/gpu.sh $T bench bench &&
-bash tools/gpu.sh $T bench bench_c5 --no-cpu-baseline --no-secondary --headline-only --config c5 --steps 10 --warmup 2 &&
-bash tools/gpu.sh $T bench bench_bm1 --no-cpu-baseline --no-secondary --headline-only --dist --decomp bitmap --steps 10 &&
+bash tools/gpu.sh $T bench bench --full &&
+bash tools/gpu.sh $T bench bench_c5 --full --no-cpu-baseline --no-secondary --headline-only --config c5 --steps 10 --warmup 2 &&
+bash tools/gpu.sh $T bench bench_bm1 --full --no-cpu-baseline --no-secondary --headline-only --dist --decomp bitmap --steps 10 &&
 bash tools/gpu.sh $T prof c3 --config c3
