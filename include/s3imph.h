@@ -173,7 +173,9 @@ int s3imph_ctx_reserve(s3imph_ctx *ctx, uint64_t max_keys, uint64_t max_global_k
 
 /* Enqueue the whole build on `stream` (a hipStream_t; NULL = the ctx's own stream,
  * a blocking stream, i.e. ordered after work queued on the legacy NULL stream) and
- * wait for it.  d_blob must be readable up to offsets[n] rounded up to 8 bytes.
+ * wait for it.  d_blob must be readable up to offsets[n] rounded up to 8 bytes and
+ * may have any byte alignment (a 16-byte aligned pointer takes the LDS-staged level-0
+ * hashes, any other one the per-lane hash; the outputs are the same bytes).
  * d_pos may be NULL (identity).  d_fp_out / d_pos_out: n entries each.
  * The level bit vectors stay on the device until s3imph_ctx_mph_bin(). */
 int s3imph_build_device(s3imph_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_offsets,
@@ -298,7 +300,8 @@ int s3imph_lookup_device(s3imph_ctx *ctx, const uint8_t *d_blob, const uint64_t 
  *       depth_positions.u64       positions grouped by depth, ascending in a depth.
  *     Positions are the Add order 0..n-1 (indexbuild.go:160).  The prefixes must be
  *     byte-sorted (the reference's Add order); the blob on the device is readable up to
- *     round_up(offsets[n], 8) as for the build.
+ *     round_up(offsets[n], 8) as for the build, and like the build's (and the lookup's)
+ *     d_blob it may have any byte alignment.
  * ------------------------------------------------------------------------ */
 /* Replaces DepthIndexBuilder.Build + writeSubtreeArrays + the depth.u32 writer: computes
  * on `device` and writes the five files into out_dir (S3ID framing, format.go:25-32). */

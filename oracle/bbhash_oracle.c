@@ -280,12 +280,14 @@ int orc_build(const uint8_t *blob, const uint64_t *offsets, const uint64_t *pos,
     uint64_t *kh = (uint64_t *)malloc(n * sizeof(uint64_t));
     uint64_t *fp = (uint64_t *)malloc(n * sizeof(uint64_t));
     orc_hash_keys(blob, offsets, n, kh, fp);
-    for (uint64_t i = 0; i < n; i++) {
-        if (kh[i] == 0) { free(kh); free(fp); return ORC_ERR_KEY_ZERO; }
-    }
+    /* Duplicates before the zero key hash: the reference fails in bbhash.New
+     * (mphf_streaming.go:141-144) before it reaches the Key() == 0 loop (:248-252). */
     orc_mphf *m = NULL;
     int st = orc_bbhash_new(kh, n, &m);
     if (st != ORC_OK) { free(kh); free(fp); return st; }
+    for (uint64_t i = 0; i < n; i++) {
+        if (kh[i] == 0) { free(kh); free(fp); orc_free(m); return ORC_ERR_KEY_ZERO; }
+    }
     for (uint64_t i = 0; i < n; i++) {
         uint64_t v = orc_find(m, kh[i]);
         if (v == 0 || v > n) { free(kh); free(fp); orc_free(m); return ORC_ERR_INTERNAL; }
@@ -385,11 +387,11 @@ int orc_build_mt(const uint8_t *blob, const uint64_t *offsets, const uint64_t *p
     c.kh = (uint64_t *)malloc(n * sizeof(uint64_t));
     c.fp = (uint64_t *)malloc(n * sizeof(uint64_t));
     orc_par_for(n, nthreads, orc_mt_hash, &c);
-    for (uint64_t i = 0; i < n; i++)
-        if (c.kh[i] == 0) { free(c.kh); free(c.fp); return ORC_ERR_KEY_ZERO; }
     orc_mphf *m = NULL;
-    int st = orc_bbhash_new(c.kh, n, &m);
+    int st = orc_bbhash_new(c.kh, n, &m);  /* duplicates first, as orc_build */
     if (st != ORC_OK) { free(c.kh); free(c.fp); return st; }
+    for (uint64_t i = 0; i < n; i++)
+        if (c.kh[i] == 0) { free(c.kh); free(c.fp); orc_free(m); return ORC_ERR_KEY_ZERO; }
     c.m = m;
     orc_par_for(n, nthreads, orc_mt_place, &c);
     free(c.kh);
@@ -444,8 +446,8 @@ int orc_build_revmap(const uint8_t *blob, const uint64_t *offsets, const uint64_
     uint64_t *kh = (uint64_t *)malloc(n * sizeof(uint64_t));
     uint64_t *fp = (uint64_t *)malloc(n * sizeof(uint64_t));
     orc_hash_keys(blob, offsets, n, kh, fp);
-    int status = ORC_OK;
-    for (uint64_t i = 0; i < n; i++) if (kh[i] == 0) { status = ORC_ERR_KEY_ZERO; break; }
+    int status = ORC_OK, zero = 0;
+    for (uint64_t i = 0; i < n; i++) if (kh[i] == 0) { zero = 1; break; }
     uint64_t *rev = (uint64_t *)malloc(n * sizeof(uint64_t));   /* rank -> key hash */
     uint64_t *cur = (uint64_t *)malloc(n * sizeof(uint64_t));
     uint64_t *nxt = (uint64_t *)malloc(n * sizeof(uint64_t));
@@ -478,6 +480,9 @@ int orc_build_revmap(const uint8_t *blob, const uint64_t *offsets, const uint64_
         uint64_t *t = cur; cur = nxt; nxt = t;
         ncur = nn;
     }
+    /* the level loop (bbhash.New, mphf_streaming.go:141-144) fails on duplicates before the
+     * Key() == 0 check of computeHashPositionsReverseMap (:248-252) is reached */
+    if (status == ORC_OK && zero) status = ORC_ERR_KEY_ZERO;
     if (status == ORC_OK) {
         orc_map mp;
         orc_map_init(&mp, n);

@@ -21,7 +21,16 @@ def test_gpus_n_without_torchrun_spawns_ranks():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--probe-launch",
                         "--steps", "2"], capture_output=True, text=True, env=_env(), timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    # the ranks share one stdout, and a report and its newline are separate writes: two
+    # reports may land on one line, so take every JSON object of each such line
+    lines, dec = [], json.JSONDecoder()
+    for x in r.stdout.splitlines():
+        at = 0 if x.startswith("{") else -1
+        while at != -1:
+            obj, end = dec.raw_decode(x, at)
+            lines.append(obj)
+            at = x.find("{", end)
+    assert len(lines) == 3
     assert sorted(x["rank"] for x in lines) == [0, 1, 2]
     assert all(x["world"] == 3 and x["gpus"] == 3 for x in lines)
     assert sorted(x["local_rank"] for x in lines) == [0, 1, 2]

@@ -34,10 +34,26 @@ def ctx(s3):
     c.close()
 
 
-def _device_build(s3, ctx, blob, offs, pos=None):
+def _misaligned_dev(a, shift):
+    """`a` (u8) `shift` bytes into a zeroed, 16-byte aligned device allocation: a view whose
+    data pointer is `shift` mod 16, readable to round_up(len(a), 8) and beyond."""
+    import torch
+    a = np.ascontiguousarray(a, np.uint8)
+    buf = torch.zeros(shift + (len(a) + 7) // 8 * 8 + 16, dtype=torch.uint8, device="cuda")
+    buf[shift:shift + len(a)] = torch.from_numpy(a.copy()).to("cuda")
+    view = buf[shift:]
+    assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == shift
+    return view
+
+
+def _device_build(s3, ctx, blob, offs, pos=None, shift=0):
     import torch
     n = len(offs) - 1
-    d_blob = to_dev(np.ascontiguousarray(blob, np.uint8), pad8=True)
+    if shift:  # a device pointer that is not 16-byte aligned: the per-lane level-0 hash
+        d_blob = _misaligned_dev(blob, shift)
+        assert d_blob.data_ptr() % 16 != 0
+    else:
+        d_blob = to_dev(np.ascontiguousarray(blob, np.uint8), pad8=True)
     d_offs = to_dev(offs)
     d_pos = to_dev(pos) if pos is not None else None
     d_fp = torch.zeros(max(n, 1), dtype=torch.int64, device="cuda")
@@ -302,12 +318,18 @@ def test_very_long_keys_mixed(s3, oracle_lib, ctx):
 
 
 def test_unaligned_blob_offsets(s3, oracle_lib, ctx):
-    """Keys starting at every byte phase, including a non-zero offsets[0]."""
+    """Keys starting at every byte phase, including a non-zero offsets[0]: in a 16-byte
+    aligned device allocation (the copy realigns the pointer: only the offsets are odd),
+    then at a device pointer that itself is 3 mod 16 (k_hash_count0)."""
     keys = [bytes([65 + (i % 26)] * (i % 19)) + b"%d/" % i for i in range(5000)]
     blob, offs = O.keys_to_blob(keys)
     shifted = np.concatenate([np.frombuffer(b"zzz", np.uint8), blob])
     st, fp, po, mph = oracle_lib.build(blob, offs)
     gfp, gpo, gmph, _ = _device_build(s3, ctx, shifted, offs + 3)
+    assert gmph == mph and np.array_equal(gfp, fp) and np.array_equal(gpo, po)
+    gfp, gpo, gmph, _ = _device_build(s3, ctx, shifted, offs + 3, shift=3)
+    assert gmph == mph and np.array_equal(gfp, fp) and np.array_equal(gpo, po)
+    gfp, gpo, gmph, _ = _device_build(s3, ctx, blob, offs, shift=3)
     assert gmph == mph and np.array_equal(gfp, fp) and np.array_equal(gpo, po)
 
 
@@ -591,8 +613,9 @@ def test_big_tiles_bit_exact(s3, oracle_lib):
 def test_p0_level0_bit_exact(s3, oracle_lib, n, unaligned):
     """Level 0 with more than 2048 tiles of 2^14 positions (P0, s3imph_internal.h): the
     records go to super-tile slots, then to their tiles' slots, then the pipelined register
-    tiles (k_tile_p0).  Just past the threshold (2051 tiles), and an unaligned blob whose
-    level-0 hash is k_hash_count0 (kh / fp, then the partition pass); 5 / 10 super-tiles
+    tiles (k_tile_p0).  Just past the threshold (2051 tiles), and a blob at a device pointer
+    that is 1 mod 16 (asserted in _device_build), whose level-0 hash is k_hash_count0 (kh / fp,
+    then the partition pass) instead of the fused k_hash0_pair<.., PT>; 5 / 10 super-tiles
     (blocks per super-tile a multiple of the 8 XCD shards, ~768 in all).  Bit-exact, and the build's
     last attempt is P0's (no conservative rerun: its stage marks are P0's)."""
     c = s3.DeviceBuilder(0)
@@ -603,7 +626,7 @@ def test_p0_level0_bit_exact(s3, oracle_lib, n, unaligned):
         assert st == 0
         c.set_profiling(1)
         if unaligned:
-            gfp, gpo, gmph, _ = _device_build(s3, c, np.concatenate([np.frombuffer(b"q", np.uint8), blob]), offs + 1)
+            gfp, gpo, gmph, _ = _device_build(s3, c, blob, offs, shift=1)
         else:
             gfp, gpo, gmph, _ = _device_build(s3, c, blob, offs)
         assert gmph == mph and np.array_equal(gfp, fp) and np.array_equal(gpo, po)

@@ -182,6 +182,50 @@ def test_build_mt_and_revmap_report_duplicates(oracle_lib):
     assert oracle_lib.build_revmap(blob, offs)[0] == st
 
 
+# Keys whose FNV-1a-64 is 0 (the reverse-map sentinel, mphf_streaming.go:248-252).
+ZERO_HASH_KEYS = [b"!0IC=VloaY", b"77kepQFQ8Kl", bytes.fromhex("d56bb95342870836")]
+
+
+@pytest.mark.parametrize("key", ZERO_HASH_KEYS, ids=["len10", "len11", "len8"])
+def test_zero_hash_preimages(oracle_lib, key):
+    assert O.py_fnv1a64(key) == 0
+    assert oracle_lib.fnv1a64(key) == 0
+    assert oracle_lib.fnv1_64(key) == O.py_fnv1_64(key) != 0
+
+
+def _all_builds(oracle_lib, keys):
+    blob, offs = O.keys_to_blob(keys)
+    return [oracle_lib.build(blob, offs)[0], oracle_lib.build_mt(blob, offs, threads=8)[0],
+            oracle_lib.build_revmap(blob, offs)[0]]
+
+
+@pytest.mark.parametrize("n", [1, 5000])
+@pytest.mark.parametrize("where", ["first", "middle", "last"])
+def test_zero_key_hash_is_reported(oracle_lib, n, where):
+    """A key whose FNV-1a hash is 0 fails every oracle build with ORC_ERR_KEY_ZERO
+    (mphf_streaming.go:248-252), wherever it stands."""
+    keys = [b"z/%06d/" % i for i in range(n)]
+    keys[{"first": 0, "middle": n // 2, "last": n - 1}[where]] = ZERO_HASH_KEYS[0]
+    assert _all_builds(oracle_lib, keys) == [O.ORC_ERR_KEY_ZERO] * 3
+
+
+@pytest.mark.parametrize("order", ["zero_then_dup", "dup_then_zero"])
+def test_duplicates_take_precedence_over_zero_key_hash(oracle_lib, order):
+    """A set with both a zero-hash key and a duplicate pair: the reference fails in bbhash.New
+    (mphf_streaming.go:141-144) before it reaches the Key() == 0 loop (:248-252), so every
+    oracle build reports the duplicates, whichever comes first in key order; without the
+    duplicate the same set reports the zero key hash."""
+    keys = [b"z/%06d/" % i for i in range(5000)]
+    zi, di = (10, 4000) if order == "zero_then_dup" else (4000, 10)
+    keys[zi] = ZERO_HASH_KEYS[1]
+    clean = list(keys)
+    keys[di] = keys[di + 1]
+    assert _all_builds(oracle_lib, keys) == [O.ORC_ERR_TOO_MANY_LEVELS] * 3
+    assert _all_builds(oracle_lib, clean) == [O.ORC_ERR_KEY_ZERO] * 3
+    # two copies of the zero-hash key itself are duplicates too
+    assert _all_builds(oracle_lib, clean + [ZERO_HASH_KEYS[1]]) == [O.ORC_ERR_TOO_MANY_LEVELS] * 3
+
+
 def test_custom_pos_permutes_with_keys(oracle_lib):
     """Add(prefix, pos) accepts arbitrary pos (mphf_streaming.go:68); pos_out[p] = pos_i."""
     keys = [("k%d/" % i).encode() for i in range(300)]
