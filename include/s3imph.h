@@ -336,6 +336,114 @@ int s3imph_verify_manifest(const char *dir, char *err, size_t errlen);
 int s3imph_sha256_file(const char *path, int portable, char hex_out[65], char *err, size_t errlen);
 
 /* ------------------------------------------------------------------------
+ * 5c. indexread.Index (pkg/indexread/index.go): an index opened on the GPU and the
+ *     reader's queries answered for a whole batch per call.  The arrays of sections 1-5b
+ *     live in HBM; a handle owns an internal s3imph_ctx for the MPHF levels and the
+ *     rank directory (s3imph_ctx_load_mph_bin / s3imph_lookup_device).
+ *
+ *     The reference's Index allows concurrent readers (index.go:13-16).  Here the calls
+ *     on one handle are serialised by a mutex; open several handles for concurrency.
+ *     Every query call waits for its stream before it returns.
+ *
+ *     Differences from the reference's Open, both deliberate:
+ *       - object_count.u64 and total_bytes.u64 are optional (Open requires them,
+ *         index.go:46-56): this project's pipeline does not write them, they are the
+ *         caller's aggregation data.  Without them object_count / total_bytes read 0 and
+ *         a non-zero filter returns S3IMPH_ERR_STATE.  Tier stats are out of scope.
+ *       - Open validates the values, not only the headers (the reference trusts the
+ *         files): see s3imph_index_open.  No kernel is ever handed an index that could
+ *         make it read out of bounds.
+ * ------------------------------------------------------------------------ */
+typedef struct s3imph_index s3imph_index;
+
+/* Open(dir) — pkg/indexread/index.go:31-86.  Reads subtree_end.u64, depth.u32,
+ * max_depth_in_subtree.u32, depth_offsets.u64, depth_positions.u64 (OpenDepthIndex,
+ * depthindex.go:115-141), mph.bin, mph_fp.u64, mph_pos.u64 (OpenMPHF, mphf.go:186-247) and,
+ * when both are present, object_count.u64 / total_bytes.u64; every array's S3ID header is
+ * checked as OpenArray does (reader.go:81-119), plus the element width.  Error texts follow
+ * the reference ("open subtree_end: ...", "open depth: ...", "open depth index: ...",
+ * "open MPHF: ..."): a missing file is S3IMPH_ERR_IO, a bad header S3IMPH_ERR_FORMAT.
+ * All validation happens on the host, before the device is selected or anything is
+ * allocated on it.  S3IMPH_ERR_FORMAT unless, beyond the headers:
+ *   - subtree_end, depth, max_depth_in_subtree, mph_fp, mph_pos (and the two stats files
+ *     when present) hold the same count n, and mph.bin's levels hold n keys;
+ *   - depth_offsets has at least 2 entries, starts at 0, never decreases and ends at the
+ *     count of depth_positions; maxDepth = its count - 2 (depthindex.go:130-134);
+ *   - every depth[i] <= maxDepth, every depth_positions[i] < n, every mph_pos[i] < n.
+ * The empty index (0-byte mph.bin, count-0 arrays, depth_offsets = [0, 0]) opens with
+ * Count() = 0. */
+int s3imph_index_open(int device, const char *dir, s3imph_index **out, char *err, size_t errlen);
+
+/* The same over arrays already in HBM (borrowed: they must outlive the handle), e.g. straight
+ * after s3imph_build_device + s3imph_finalize_index_device.  mph_bin is host bytes
+ * (s3imph_ctx_mph_bin); d_object_count / d_total_bytes are nullable (both or neither).
+ * The invariants s3imph_index_open checks are taken on trust here — the caller just built
+ * the arrays; only null pointers and mph.bin's framing are checked. */
+typedef struct s3imph_index_arrays {
+    const uint8_t *mph_bin; uint64_t mph_len;
+    uint64_t n;                       /* nodes */
+    const uint64_t *d_fp, *d_pos;     /* mph_fp / mph_pos */
+    const uint32_t *d_depth, *d_max_depth_in_subtree;
+    const uint64_t *d_subtree_end, *d_depth_offsets, *d_depth_positions;
+    uint32_t max_depth;               /* depth_offsets has max_depth + 2 entries */
+    const uint64_t *d_object_count, *d_total_bytes;
+} s3imph_index_arrays;
+int s3imph_index_attach(int device, const s3imph_index_arrays *a, s3imph_index **out, char *err, size_t errlen);
+
+/* Close() — index.go:108-119.  idx is invalid afterwards. */
+int s3imph_index_close(s3imph_index *idx);
+/* Count() — index.go:188. */
+uint64_t s3imph_index_count(const s3imph_index *idx);
+/* MaxDepth() — index.go:193. */
+uint64_t s3imph_index_max_depth(const s3imph_index *idx);
+/* Message of the last failed call on idx ("" if none). */
+const char *s3imph_index_last_error(s3imph_index *idx);
+
+/* Lookup — index.go:128 (MPHF.Lookup, mphf.go:275-302): nq query keys in the blob / offsets
+ * layout (d_blob readable up to offsets[nq] rounded up to 8, any byte alignment);
+ * d_pos_out[i] = pos, or UINT64_MAX when not found. */
+int s3imph_index_lookup_device(s3imph_index *idx, const uint8_t *d_blob, const uint64_t *d_offsets,
+                               uint64_t nq, uint64_t *d_pos_out, void *stream);
+
+/* Stats / Depth / SubtreeEnd / MaxDepthInSubtree — index.go:135-176 — for nq positions.
+ * pos >= Count() (the UINT64_MAX of a failed lookup included) gives an all-zero record with
+ * found = 0, as those methods return zero; lookup followed by nodes is StatsForPrefix
+ * (index.go:146-152). */
+typedef struct s3imph_node {
+    uint64_t pos, subtree_end, object_count, total_bytes;
+    uint32_t depth, max_depth_in_subtree, found, pad;
+} s3imph_node;
+int s3imph_index_nodes_device(s3imph_index *idx, const uint64_t *d_qpos, uint64_t nq,
+                              s3imph_node *d_out, void *stream);
+
+/* DescendantsAtDepth[Filtered] / DescendantsUpToDepth — index.go:206-297 — as a CSR over the
+ * batch, in two steps: plan computes d_levels (per query, the number of result rows the
+ * reference returns; 0 = nil) and d_row_ptr (n_rows + 1 entries, the exclusive prefix of the
+ * row lengths; *total = row_ptr[n_rows]); fill writes the positions of the last plan, row
+ * after row, into d_out[0 .. total).
+ *   S3IMPH_DESC_AT:   d_rel[q] = relDepth of query q; n_rows = nq.  levels = 0 when
+ *     pos >= Count(), rel < 0 or depth[pos] + rel > maxDepth (index.go:207-219), else 1 and the
+ *     row holds the positions p at that depth with pos <= p <= subtree_end[pos], in order
+ *     (GetPositionsInSubtree, depthindex.go:193-259); a non-zero filter keeps the p with
+ *     object_count[p] >= min_count && total_bytes[p] >= min_bytes (index.go:283-295).
+ *   S3IMPH_DESC_UPTO: d_rel NULL, max_rel for the whole batch; R = min(max(max_rel, 0),
+ *     maxDepth) rows per query, n_rows = nq * R, row q * R + j is depth depth[pos] + 1 + j;
+ *     levels[q] = min(max_depth_in_subtree[pos] - depth[pos], max_rel), or 0 when that is
+ *     <= 0 or pos >= Count() (index.go:239-268); rows j >= levels[q] are empty.  A filter
+ *     with UPTO is S3IMPH_ERR_INVALID.
+ * plan returns S3IMPH_ERR_INVALID when row_ptr_cap < n_rows + 1 or n_rows >= 2^31; nq == 0
+ * or n_rows == 0 is OK with *total = 0.  fill returns S3IMPH_ERR_INVALID when cap < total and
+ * S3IMPH_ERR_STATE without a plan; a later plan replaces the earlier one. */
+#define S3IMPH_DESC_AT   0
+#define S3IMPH_DESC_UPTO 1
+int s3imph_index_descendants_plan(s3imph_index *idx, const uint64_t *d_qpos, const int32_t *d_rel,
+                                  uint64_t nq, int mode, int32_t max_rel,
+                                  uint64_t min_count, uint64_t min_bytes,
+                                  int32_t *d_levels /* nq */, uint64_t *d_row_ptr /* n_rows + 1 */,
+                                  uint64_t row_ptr_cap, uint64_t *n_rows, uint64_t *total, void *stream);
+int s3imph_index_descendants_fill(s3imph_index *idx, uint64_t *d_out, uint64_t cap, void *stream);
+
+/* ------------------------------------------------------------------------
  * 6. Deterministic synthetic prefix sets (bench/test support, not on the path).
  *    kind: 0 = s3-like, lengths uniform in [max(10, avg/2), 3avg/2],
  *              distinct and byte-sorted;

@@ -1,0 +1,926 @@
+// s3imph_index.hip — indexread.Index on the GPU (include/s3imph.h section 5c): an index
+// handle whose arrays live in HBM, and batched forms of the reference reader's queries.
+//
+// Reference (pkg/indexread/index.go, pkg/format/depthindex.go):
+//   Open                       index.go:31-86 (OpenArray, reader.go:81-119; OpenDepthIndex,
+//                              depthindex.go:115-141; OpenMPHF, mphf.go:186-247);
+//   Lookup / StatsForPrefix    index.go:128-152;
+//   Stats / Depth / SubtreeEnd / MaxDepthInSubtree   index.go:135-176;
+//   DescendantsAtDepth[Filtered] / DescendantsUpToDepth   index.go:206-297, over
+//   GetPositionsInSubtree (depthindex.go:193-259, two binary searches in a depth's slice).
+//
+// GPU formulation.  A batch of descendants queries is a CSR: `levels` per query, `row_ptr`
+// over the result rows, and the flat list of positions.  The plan step runs one lane per
+// row (the two binary searches side by side, so two dependent loads are in flight per
+// lane; occupancy hides the rest) and scans the row lengths with a reduce / top / down
+// triple.  Row lengths run from 0 to the whole index, so nothing after that is
+// decomposed by row: the OUTPUT is cut into chunks of kChunk positions, one workgroup
+// each, and every lane finds the row of its own output slot by a binary search in
+// row_ptr over the few rows its chunk touches.  The filter works on the same chunks of
+// the unfiltered list: flags are counted per chunk, the chunk counts scanned, the filtered
+// row_ptr read off the flag prefix at each row's start, and the fill writes each kept
+// position at its flag prefix (order kept).  No kernel here waits on another workgroup.
+#include <sys/stat.h>
+
+#include <cerrno>
+#include <cstdio>
+#include <cstring>
+
+#include "s3imph_ctx.h"
+#include "s3imph_device.h"
+
+namespace s3imph {
+namespace {
+
+constexpr int kQT = 256;                   // lanes per workgroup of the per-query / per-row kernels
+constexpr int kScanT = 256;                // row-length scan: 8 values per lane
+constexpr int kScanPer = 8;
+constexpr int kScanB = kScanT * kScanPer;  // values per scan block
+constexpr int kChunkT = 256;               // the chunk kernels: kChunk / kChunkT slots per lane
+constexpr int kChunk = 2048;               // output positions per chunk (a power of two)
+constexpr int kChunkPer = kChunk / kChunkT;
+
+struct IndexArrays {
+  uint64_t n = 0;
+  uint32_t max_depth = 0;
+  const uint64_t *fp = nullptr, *pos = nullptr;
+  const uint32_t *depth = nullptr, *mds = nullptr;
+  const uint64_t *send = nullptr, *doff = nullptr, *dpos = nullptr;
+  const uint64_t *ocnt = nullptr, *tbytes = nullptr;  // nullable
+};
+
+// Stats / Depth / SubtreeEnd / MaxDepthInSubtree for one position per lane; zero record
+// with found = 0 when pos >= Count() (index.go:135-176).
+__global__ __launch_bounds__(kQT) void k_index_nodes(IndexArrays a, const uint64_t* __restrict__ qpos, uint64_t nq,
+                                                     s3imph_node* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * kQT + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t p = qpos[i];
+  s3imph_node r{};
+  if (p < a.n) {
+    r.pos = p;
+    r.subtree_end = a.send[p];
+    r.object_count = a.ocnt ? a.ocnt[p] : 0;
+    r.total_bytes = a.tbytes ? a.tbytes[p] : 0;
+    r.depth = a.depth[p];
+    r.max_depth_in_subtree = a.mds[p];
+    r.found = 1;
+  }
+  out[i] = r;
+}
+
+// One lane per result row: the row's slice start in depth_positions and its unfiltered
+// length; lane j == 0 of a query writes its `levels`.  AT: rel[q] levels below the query;
+// UPTO: row j of query q is depth[pos] + 1 + j (R rows per query).
+__global__ __launch_bounds__(kQT) void k_desc_ranges(IndexArrays a, const uint64_t* __restrict__ qpos,
+                                                     const int32_t* __restrict__ rel, uint64_t n_rows, int upto,
+                                                     uint32_t R, int32_t max_rel, int32_t* __restrict__ levels,
+                                                     uint64_t* __restrict__ row_lo, uint64_t* __restrict__ row_len) {
+  const uint64_t row = (uint64_t)blockIdx.x * kQT + threadIdx.x;
+  if (row >= n_rows) return;
+  const uint64_t q = upto ? row / R : row;
+  const uint32_t j = upto ? (uint32_t)(row % R) : 0;
+  const uint64_t pos = qpos[q];
+  int32_t lv = 0;
+  uint64_t lo = 0, len = 0;
+  if (pos < a.n) {
+    const uint64_t d = a.depth[pos];
+    uint64_t t;
+    bool ok;
+    if (upto) {
+      const int64_t diff = (int64_t)a.mds[pos] - (int64_t)d;
+      const int64_t l = diff < (int64_t)max_rel ? diff : (int64_t)max_rel;
+      lv = l <= 0 ? 0 : (l > (int64_t)R ? (int32_t)R : (int32_t)l);
+      ok = (int64_t)j < (int64_t)lv;
+      t = d + 1 + j;
+    } else {
+      const int32_t r = rel[q];
+      t = d + (uint64_t)(r < 0 ? 0 : r);  // no wrap-around: d < 2^32, r < 2^31
+      ok = r >= 0 && t <= (uint64_t)a.max_depth;
+      lv = ok ? 1 : 0;
+    }
+    ok = ok && t <= (uint64_t)a.max_depth;
+    if (ok) {
+      const uint64_t s = a.doff[t], e = a.doff[t + 1], se = a.send[pos];
+      // first index with p >= pos and first with p > subtree_end, both over [s, e): the two
+      // searches advance together, selects instead of exits
+      uint64_t l0 = s, n0 = e > s ? e - s : 0, l1 = l0, n1 = n0;
+      while (n0 | n1) {
+        const uint64_t h0 = n0 >> 1, h1 = n1 >> 1;
+        const uint64_t v0 = n0 ? a.dpos[l0 + h0] : 0, v1 = n1 ? a.dpos[l1 + h1] : 0;
+        const bool r0 = n0 && v0 < pos, r1 = n1 && v1 <= se;
+        l0 = r0 ? l0 + h0 + 1 : l0;
+        n0 = r0 ? n0 - h0 - 1 : h0;
+        l1 = r1 ? l1 + h1 + 1 : l1;
+        n1 = r1 ? n1 - h1 - 1 : h1;
+      }
+      lo = l0;
+      len = l1 > l0 ? l1 - l0 : 0;
+    }
+  }
+  if (j == 0) levels[q] = lv;
+  row_lo[row] = lo;
+  row_len[row] = len;
+}
+
+// ---- exclusive scan of n u64 values into n + 1 entries: reduce / top / down --------------
+__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t u = __shfl_up((unsigned long long)v, o);
+    if ((int)lane_id() >= o) v += u;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(kScanT) void k_rows_reduce(const uint64_t* __restrict__ in, uint64_t n,
+                                                        uint64_t* __restrict__ sums) {
+  __shared__ uint64_t s_w[kScanT / 64];
+  const uint64_t b0 = (uint64_t)blockIdx.x * kScanB;
+  uint64_t v = 0;
+#pragma unroll
+  for (int k = 0; k < kScanPer; ++k) {
+    const uint64_t i = b0 + threadIdx.x + (uint64_t)k * kScanT;
+    if (i < n) v += in[i];
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor((unsigned long long)v, o);
+  if (lane_id() == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t t = 0;
+    for (int w = 0; w < kScanT / 64; ++w) t += s_w[w];
+    sums[blockIdx.x] = t;
+  }
+}
+
+// One workgroup: sums[0 .. nb) -> exclusive prefix in place, sums[nb] = total.
+__global__ __launch_bounds__(1024) void k_rows_top(uint64_t* __restrict__ sums, uint64_t nb) {
+  __shared__ uint64_t s_w[16];
+  __shared__ uint64_t s_carry;
+  if (threadIdx.x == 0) s_carry = 0;
+  __syncthreads();
+  for (uint64_t b0 = 0; b0 < nb; b0 += 1024) {
+    const uint64_t i = b0 + threadIdx.x;
+    const uint64_t v = i < nb ? sums[i] : 0;
+    const uint64_t inc = wave_incl_scan(v);
+    if (lane_id() == 63) s_w[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    uint64_t base = s_carry;
+    for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) base += s_w[w];
+    if (i < nb) sums[i] = base + inc - v;
+    __syncthreads();
+    if (threadIdx.x == 1023) s_carry = base + inc;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) sums[nb] = s_carry;
+}
+
+// out[i] (and out2[i] when given) = sums[block] + prefix inside the block; entry n = total.
+__global__ __launch_bounds__(kScanT) void k_rows_down(const uint64_t* __restrict__ in, uint64_t n,
+                                                      const uint64_t* __restrict__ sums, uint64_t nb,
+                                                      uint64_t* __restrict__ out, uint64_t* __restrict__ out2) {
+  __shared__ uint64_t s_w[kScanT / 64];
+  const uint64_t i0 = (uint64_t)blockIdx.x * kScanB + (uint64_t)threadIdx.x * kScanPer;
+  uint64_t v[kScanPer], tot = 0;
+#pragma unroll
+  for (int k = 0; k < kScanPer; ++k) {
+    v[k] = i0 + k < n ? in[i0 + k] : 0;
+    tot += v[k];
+  }
+  const uint64_t inc = wave_incl_scan(tot);
+  if (lane_id() == 63) s_w[threadIdx.x >> 6] = inc;
+  __syncthreads();
+  uint64_t run = sums[blockIdx.x] + inc - tot;
+  for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) run += s_w[w];
+#pragma unroll
+  for (int k = 0; k < kScanPer; ++k) {
+    if (i0 + k < n) {
+      out[i0 + k] = run;
+      if (out2) out2[i0 + k] = run;
+    }
+    run += v[k];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    out[n] = sums[nb];
+    if (out2) out2[n] = sums[nb];
+  }
+}
+
+// ---- the chunk kernels ---------------------------------------------------------------------
+// First index in [lo, hi) with U[index] > u, or hi.
+__device__ __forceinline__ uint64_t first_above(const uint64_t* __restrict__ U, uint64_t lo, uint64_t hi,
+                                                uint64_t u) {
+  uint64_t len = hi - lo;
+  while (len) {
+    const uint64_t h = len >> 1;
+    const bool right = U[lo + h] <= u;
+    lo = right ? lo + h + 1 : lo;
+    len = right ? len - h - 1 : h;
+  }
+  return lo;
+}
+// First index in [lo, hi) with U[index] >= u, or hi.
+__device__ __forceinline__ uint64_t first_at_least(const uint64_t* __restrict__ U, uint64_t lo, uint64_t hi,
+                                                   uint64_t u) {
+  uint64_t len = hi - lo;
+  while (len) {
+    const uint64_t h = len >> 1;
+    const bool right = U[lo + h] < u;
+    lo = right ? lo + h + 1 : lo;
+    len = right ? len - h - 1 : h;
+  }
+  return lo;
+}
+
+// The rows a chunk [base, end) of the flat list touches (end > base): the row of slot u is
+// the last r with U[r] <= u (empty rows share their successor's start and are never that
+// one); U has n_rows + 1 entries, U[n_rows] = total >= end.
+struct ChunkRows {
+  uint64_t r0, r1;
+};
+__device__ __forceinline__ ChunkRows chunk_rows(const uint64_t* __restrict__ U, uint64_t n_rows, uint64_t base,
+                                                uint64_t end) {
+  ChunkRows c;
+  c.r0 = first_above(U, 0, n_rows + 1, base) - 1;
+  c.r1 = first_above(U, c.r0 + 1, n_rows + 1, end - 1) - 1;
+  return c;
+}
+// The position at slot u of the flat list, u in the chunk whose rows are c.
+__device__ __forceinline__ uint64_t slot_position(const uint64_t* __restrict__ U, const uint64_t* __restrict__ row_lo,
+                                                  const uint64_t* __restrict__ dpos, ChunkRows c, uint64_t u) {
+  const uint64_t r = first_above(U, c.r0 + 1, c.r1 + 1, u) - 1;
+  return dpos[row_lo[r] + (u - U[r])];
+}
+
+// Unfiltered fill: out[u] = position at slot u, one workgroup per chunk of the output.
+__global__ __launch_bounds__(kChunkT) void k_desc_fill(const uint64_t* __restrict__ U,
+                                                       const uint64_t* __restrict__ row_lo, uint64_t n_rows,
+                                                       uint64_t total, const uint64_t* __restrict__ dpos,
+                                                       uint64_t* __restrict__ out) {
+  const uint64_t base = (uint64_t)blockIdx.x * kChunk;
+  if (base >= total) return;
+  const uint64_t end = base + kChunk < total ? base + kChunk : total;
+  const ChunkRows c = chunk_rows(U, n_rows, base, end);
+#pragma unroll
+  for (int k = 0; k < kChunkPer; ++k) {
+    const uint64_t u = base + threadIdx.x + (uint64_t)k * kChunkT;
+    if (u < end) out[u] = slot_position(U, row_lo, dpos, c, u);
+  }
+}
+
+// The filter over the chunks of the unfiltered list (U, total).  Every mode flags its chunk's
+// candidates (object_count >= min_count && total_bytes >= min_bytes, unsigned) in list order.
+//   kCount: csum[chunk] = flags of the chunk.
+//   kRows:  row_ptr[r] = cbase[chunk] + flags before slot U[r], for the rows that start in the
+//           chunk (U[r] in [base, base + kChunk)); launched on total / kChunk + 1 chunks, so
+//           the rows starting at `total` are covered too.
+//   kFill:  out[cbase[chunk] + flags before u] = position at u, for flagged u.
+enum { kCount = 0, kRows = 1, kFill = 2 };
+template <int MODE>
+__global__ __launch_bounds__(kChunkT) void k_desc_filter(IndexArrays a, const uint64_t* __restrict__ U,
+                                                         const uint64_t* __restrict__ row_lo, uint64_t n_rows,
+                                                         uint64_t total, uint64_t min_count, uint64_t min_bytes,
+                                                         uint64_t* __restrict__ csum,
+                                                         const uint64_t* __restrict__ cbase,
+                                                         uint64_t* __restrict__ row_ptr, uint64_t* __restrict__ out) {
+  __shared__ unsigned s_w[kChunkT / 64];
+  __shared__ unsigned s_pre[MODE == kRows ? kChunk + 1 : 1];
+  const uint64_t base = (uint64_t)blockIdx.x * kChunk;
+  if (base > total) return;
+  const uint64_t end = base + kChunk < total ? base + kChunk : total;
+  ChunkRows c{0, 0};
+  if (end > base) c = chunk_rows(U, n_rows, base, end);
+  const uint64_t cb = MODE == kCount ? 0 : cbase[blockIdx.x];
+  const unsigned wave = threadIdx.x >> 6;
+  unsigned running = 0;
+  for (int k = 0; k < kChunkPer; ++k) {
+    const unsigned slot = threadIdx.x + (unsigned)k * kChunkT;
+    const uint64_t u = base + slot;
+    uint64_t p = 0;
+    bool flag = false;
+    if (u < end) {
+      p = slot_position(U, row_lo, a.dpos, c, u);
+      flag = p < a.n && a.ocnt[p] >= min_count && a.tbytes[p] >= min_bytes;
+    }
+    const uint64_t bal = __ballot(flag);
+    if (lane_id() == 0) s_w[wave] = (unsigned)__popcll(bal);
+    __syncthreads();
+    unsigned before = running + (unsigned)__popcll(bal & lanemask_lt()), all = 0;
+#pragma unroll
+    for (unsigned w = 0; w < kChunkT / 64; ++w) {
+      before += w < wave ? s_w[w] : 0;
+      all += s_w[w];
+    }
+    if (MODE == kRows) s_pre[slot] = before;
+    if (MODE == kFill && flag) out[cb + before] = p;
+    running += all;
+    __syncthreads();
+  }
+  if (MODE == kCount && threadIdx.x == 0) csum[blockIdx.x] = running;
+  if (MODE == kRows) {
+    if (threadIdx.x == 0) s_pre[kChunk] = running;
+    __syncthreads();
+    const uint64_t ra = first_at_least(U, 0, n_rows + 1, base);
+    const uint64_t rb = first_at_least(U, ra, n_rows + 1, base + kChunk);
+    for (uint64_t r = ra + threadIdx.x; r < rb; r += kChunkT) row_ptr[r] = cb + s_pre[U[r] - base];
+  }
+}
+
+// ---- host side: files -------------------------------------------------------------------------
+struct HostArray {
+  std::vector<uint64_t> store;  // 8-byte aligned payload
+  uint64_t count = 0;
+  const uint64_t* u64() const { return store.data(); }
+  const uint32_t* u32() const { return reinterpret_cast<const uint32_t*>(store.data()); }
+};
+
+// OpenArray (reader.go:81-119) with the expected width checked as well.
+int read_array(const std::string& path, uint32_t width, HostArray* out, std::string* msg) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) {
+    *msg = "mmap file: open file: open " + path + ": " + std::strerror(errno);
+    return S3IMPH_ERR_IO;
+  }
+  struct Close {
+    FILE* f;
+    ~Close() { std::fclose(f); }
+  } closer{f};
+  struct stat st;
+  if (::fstat(fileno(f), &st) != 0) {
+    *msg = "mmap file: stat file: " + path + ": " + std::strerror(errno);
+    return S3IMPH_ERR_IO;
+  }
+  const uint64_t size = (uint64_t)st.st_size;
+  uint8_t h[kS3idHeaderSize];
+  if (size < kS3idHeaderSize || std::fread(h, 1, sizeof h, f) != sizeof h) {
+    *msg = "invalid header";
+    return S3IMPH_ERR_FORMAT;
+  }
+  auto le = [&](int at, int bytes) {
+    uint64_t v = 0;
+    for (int b = 0; b < bytes; ++b) v |= (uint64_t)h[at + b] << (8 * b);
+    return v;
+  };
+  if (le(0, 4) != kS3idMagic) {
+    *msg = "magic number mismatch";
+    return S3IMPH_ERR_FORMAT;
+  }
+  if (le(4, 4) != kS3idVersion) {
+    *msg = "version mismatch";
+    return S3IMPH_ERR_FORMAT;
+  }
+  const uint64_t count = le(8, 8), w = le(16, 4);
+  if (w != width) {
+    *msg = "element width " + std::to_string(w) + ", want " + std::to_string(width);
+    return S3IMPH_ERR_FORMAT;
+  }
+  if (count > (size - kS3idHeaderSize) / width) {
+    *msg = "file too small: " + std::to_string(size) + " < " + std::to_string(kS3idHeaderSize) + " + " +
+           std::to_string(count) + " * " + std::to_string(width);
+    return S3IMPH_ERR_FORMAT;
+  }
+  static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "S3ID payloads are little-endian");
+  const uint64_t bytes = count * width;
+  out->store.assign((bytes + 7) / 8, 0);
+  out->count = count;
+  if (bytes && std::fread(out->store.data(), 1, bytes, f) != bytes) {
+    *msg = "read " + path + ": " + std::strerror(errno);
+    return S3IMPH_ERR_IO;
+  }
+  return S3IMPH_OK;
+}
+
+bool file_exists(const std::string& p) {
+  struct stat st;
+  return ::stat(p.c_str(), &st) == 0;
+}
+
+// MarshalBinary framing of mph.bin, as s3imph_ctx_load_mph_bin checks it, without a device.
+bool mph_bin_framed(const uint8_t* p, uint64_t len, uint64_t* keys, std::string* msg) {
+  *keys = 0;
+  if (len == 0) return true;
+  uint64_t at = 0;
+  auto get = [&](uint64_t* v) {
+    if (len - at < 8) return false;
+    std::memcpy(v, p + at, 8);
+    at += 8;
+    return true;
+  };
+  uint64_t parts = 0, nl = 0;
+  if (!get(&parts) || parts != kPartitions || !get(&nl) || nl == 0 || nl > (uint64_t)kMaxLevels) {
+    *msg = "unmarshal: bad header";
+    return false;
+  }
+  for (uint64_t L = 0; L < nl; ++L) {
+    uint64_t w = 0;
+    if (!get(&w) || w > (len - at) / 8) {
+      *msg = "unmarshal: truncated level " + std::to_string(L);
+      return false;
+    }
+    if (w == 0) {
+      *msg = "unmarshal: empty level " + std::to_string(L);
+      return false;
+    }
+    for (uint64_t q = 0; q < w; ++q) {
+      uint64_t word;
+      std::memcpy(&word, p + at + 8 * q, 8);
+      *keys += (uint64_t)__builtin_popcountll(word);
+    }
+    at += 8 * w;
+  }
+  if (at != len) {
+    *msg = "unmarshal: trailing bytes";
+    return false;
+  }
+  return true;
+}
+
+// Everything Open reads, checked on the host.
+struct HostIndex {
+  HostArray send, depth, mds, doff, dpos, fp, pos, ocnt, tbytes;
+  bool stats = false;
+  std::vector<uint8_t> mph;
+  uint64_t n = 0;
+  uint32_t max_depth = 0;
+};
+
+int load_host_index(const std::string& dir, HostIndex* h, std::string* msg) {
+  std::string m;
+  int rc;
+  auto fail = [&](const char* what, int code) {
+    *msg = std::string(what) + ": " + m;
+    return code;
+  };
+  if ((rc = read_array(dir + "/subtree_end.u64", 8, &h->send, &m))) return fail("open subtree_end", rc);
+  if ((rc = read_array(dir + "/depth.u32", 4, &h->depth, &m))) return fail("open depth", rc);
+  // the caller's aggregation data: optional here (the reference's Open requires both)
+  const bool oc = file_exists(dir + "/object_count.u64"), tb = file_exists(dir + "/total_bytes.u64");
+  if (oc != tb) {
+    m = "object_count.u64 and total_bytes.u64 must both be present or both be absent";
+    return fail(oc ? "open total_bytes" : "open object_count", S3IMPH_ERR_IO);
+  }
+  h->stats = oc;
+  if (oc) {
+    if ((rc = read_array(dir + "/object_count.u64", 8, &h->ocnt, &m))) return fail("open object_count", rc);
+    if ((rc = read_array(dir + "/total_bytes.u64", 8, &h->tbytes, &m))) return fail("open total_bytes", rc);
+  }
+  if ((rc = read_array(dir + "/max_depth_in_subtree.u32", 4, &h->mds, &m)))
+    return fail("open max_depth_in_subtree", rc);
+  if ((rc = read_array(dir + "/depth_offsets.u64", 8, &h->doff, &m))) {
+    m = "open offsets: " + m;
+    return fail("open depth index", rc);
+  }
+  if ((rc = read_array(dir + "/depth_positions.u64", 8, &h->dpos, &m))) {
+    m = "open positions: " + m;
+    return fail("open depth index", rc);
+  }
+  {
+    FILE* f = std::fopen((dir + "/mph.bin").c_str(), "rb");
+    if (!f) {
+      m = "open " + dir + "/mph.bin: " + std::strerror(errno);
+      return fail("open MPHF", S3IMPH_ERR_IO);
+    }
+    uint8_t buf[1 << 16];
+    size_t k;
+    while ((k = std::fread(buf, 1, sizeof buf, f)) > 0) h->mph.insert(h->mph.end(), buf, buf + k);
+    const bool bad = std::ferror(f) != 0;
+    std::fclose(f);
+    if (bad) {
+      m = "read " + dir + "/mph.bin";
+      return fail("open MPHF", S3IMPH_ERR_IO);
+    }
+  }
+  uint64_t mph_keys = 0;
+  if (!mph_bin_framed(h->mph.data(), h->mph.size(), &mph_keys, &m)) return fail("open MPHF", S3IMPH_ERR_FORMAT);
+  if ((rc = read_array(dir + "/mph_fp.u64", 8, &h->fp, &m))) return fail("open MPHF: open fingerprints", rc);
+  if ((rc = read_array(dir + "/mph_pos.u64", 8, &h->pos, &m))) return fail("open MPHF: open positions", rc);
+
+  // beyond the headers (stricter than the reference, which trusts the files)
+  const uint64_t n = h->send.count;
+  h->n = n;
+  auto counts = [&](const char* what, const char* name, uint64_t c) {
+    if (c == n) return true;
+    m = std::string(name) + " holds " + std::to_string(c) + " entries, subtree_end " + std::to_string(n);
+    *msg = std::string(what) + ": " + m;
+    return false;
+  };
+  if (!counts("open depth", "depth", h->depth.count)) return S3IMPH_ERR_FORMAT;
+  if (oc && !counts("open object_count", "object_count", h->ocnt.count)) return S3IMPH_ERR_FORMAT;
+  if (oc && !counts("open total_bytes", "total_bytes", h->tbytes.count)) return S3IMPH_ERR_FORMAT;
+  if (!counts("open max_depth_in_subtree", "max_depth_in_subtree", h->mds.count)) return S3IMPH_ERR_FORMAT;
+  if (!counts("open MPHF", "mph_fp", h->fp.count)) return S3IMPH_ERR_FORMAT;
+  if (!counts("open MPHF", "mph_pos", h->pos.count)) return S3IMPH_ERR_FORMAT;
+  if (mph_keys != n) {
+    m = "mph.bin holds " + std::to_string(mph_keys) + " keys, the index " + std::to_string(n);
+    return fail("open MPHF", S3IMPH_ERR_FORMAT);
+  }
+  if (n > 0xffffffffull) {
+    m = "more than 2^32-1 nodes on one GPU";
+    return fail("open subtree_end", S3IMPH_ERR_FORMAT);
+  }
+  const uint64_t no = h->doff.count;
+  const uint64_t* o = h->doff.u64();
+  if (no < 2 || no - 2 > 0xffffffffull) {
+    m = "depth_offsets needs at least 2 entries";
+    return fail("open depth index", S3IMPH_ERR_FORMAT);
+  }
+  if (o[0] != 0 || o[no - 1] != h->dpos.count) {
+    m = "depth_offsets must run from 0 to the count of depth_positions";
+    return fail("open depth index", S3IMPH_ERR_FORMAT);
+  }
+  for (uint64_t i = 1; i < no; ++i)
+    if (o[i] < o[i - 1]) {
+      m = "depth_offsets decreases at " + std::to_string(i);
+      return fail("open depth index", S3IMPH_ERR_FORMAT);
+    }
+  h->max_depth = (uint32_t)(no - 2);  // OpenDepthIndex, depthindex.go:130-134
+  const uint32_t* d = h->depth.u32();
+  for (uint64_t i = 0; i < n; ++i)
+    if (d[i] > h->max_depth) {
+      m = "depth[" + std::to_string(i) + "] exceeds maxDepth " + std::to_string(h->max_depth);
+      return fail("open depth", S3IMPH_ERR_FORMAT);
+    }
+  const uint64_t* dp = h->dpos.u64();
+  for (uint64_t i = 0; i < h->dpos.count; ++i)
+    if (dp[i] >= n) {
+      m = "depth_positions[" + std::to_string(i) + "] is not a node";
+      return fail("open depth index", S3IMPH_ERR_FORMAT);
+    }
+  const uint64_t* mp = h->pos.u64();
+  for (uint64_t i = 0; i < n; ++i)
+    if (mp[i] >= n) {
+      m = "mph_pos[" + std::to_string(i) + "] is not a node";
+      return fail("open MPHF", S3IMPH_ERR_FORMAT);
+    }
+  return S3IMPH_OK;
+}
+
+}  // namespace
+}  // namespace s3imph
+
+using namespace s3imph;
+
+// The handle: the arrays (owned after Open, borrowed after attach), a context for the MPHF
+// levels and the rank directory, and the plan / fill workspace.
+struct s3imph_index {
+  int device = 0;
+  s3imph_ctx* ctx = nullptr;
+  std::mutex mu;
+  std::string last_msg;
+  IndexArrays a;
+  std::vector<void*> owned;  // device allocations of Open
+  // workspace of the last plan: per row the slice start, the unfiltered length and the
+  // unfiltered row_ptr U (rows + 1); scan block sums; per chunk the flag counts and their prefix
+  uint64_t *row_lo = nullptr, *row_len = nullptr, *U = nullptr, *sums = nullptr;
+  uint64_t rows_cap = 0;
+  uint64_t *csum = nullptr, *cbase = nullptr, *csums2 = nullptr;
+  uint64_t chunks_cap = 0;
+  bool have_plan = false;
+  uint64_t plan_rows = 0, plan_total_u = 0, plan_total = 0, plan_mc = 0, plan_mb = 0;
+  bool plan_filtered = false;
+};
+
+namespace s3imph {
+namespace {
+
+void index_free(s3imph_index* x) {
+  if (!x) return;
+  (void)hipSetDevice(x->device);
+  if (x->ctx) (void)s3imph_ctx_destroy(x->ctx);  // drains its stream first
+  for (void* p : x->owned)
+    if (p) (void)hipFree(p);
+  for (uint64_t** p : {&x->row_lo, &x->row_len, &x->U, &x->sums, &x->csum, &x->cbase, &x->csums2}) dfree(*p);
+  delete x;
+}
+
+template <typename T>
+const T* upload(s3imph_index* x, const T* host, uint64_t count) {
+  void* v = nullptr;
+  HIPCHECK(hipMalloc(&v, std::max<uint64_t>(count, 1) * sizeof(T)));
+  x->owned.push_back(v);
+  if (count) HIPCHECK(hipMemcpy(v, host, count * sizeof(T), hipMemcpyHostToDevice));
+  return static_cast<const T*>(v);
+}
+
+// A handle on `device` with the MPHF loaded; throws Fail.
+s3imph_index* index_new(int device, const uint8_t* mph, uint64_t mph_len, uint64_t n) {
+  s3imph_index* x = new s3imph_index();
+  x->device = device;
+  try {
+    char err[256] = "";
+    int rc = s3imph_ctx_create(device, &x->ctx, err, sizeof err);
+    if (rc != S3IMPH_OK) throw Fail{rc, err};
+    rc = s3imph_ctx_load_mph_bin(x->ctx, mph_len ? mph : nullptr, mph_len);
+    if (rc != S3IMPH_OK) {
+      const std::string m = s3imph_ctx_last_error(x->ctx);
+      throw Fail{rc, m.empty() ? std::string("open MPHF: ") + s3imph_status_string(rc) : m};
+    }
+    if (x->ctx->last_n != n)
+      throw Fail{S3IMPH_ERR_FORMAT, "open MPHF: mph.bin holds " + std::to_string(x->ctx->last_n) + " keys, the index " +
+                                        std::to_string(n)};
+    return x;
+  } catch (...) {
+    index_free(x);
+    throw;
+  }
+}
+
+uint64_t scan_blocks(uint64_t n) { return (n + kScanB - 1) / kScanB; }
+
+// out[0 .. n] (and out2) = exclusive prefix of in[0 .. n); sums: scan_blocks(n) + 1 words.
+void launch_rows_scan(const uint64_t* in, uint64_t n, uint64_t* sums, uint64_t* out, uint64_t* out2, hipStream_t s) {
+  const uint64_t nb = scan_blocks(n);
+  if (nb == 0) return;
+  k_rows_reduce<<<(unsigned)nb, kScanT, 0, s>>>(in, n, sums);
+  k_rows_top<<<1, 1024, 0, s>>>(sums, nb);
+  k_rows_down<<<(unsigned)nb, kScanT, 0, s>>>(in, n, sums, nb, out, out2);
+}
+
+void ensure_rows(s3imph_index* x, uint64_t rows) {
+  if (rows <= x->rows_cap) return;
+  x->rows_cap = 0;
+  dalloc(x->row_lo, rows);
+  dalloc(x->row_len, rows);
+  dalloc(x->U, rows + 1);
+  dalloc(x->sums, scan_blocks(rows) + 1);
+  x->rows_cap = rows;
+}
+
+void ensure_chunks(s3imph_index* x, uint64_t chunks) {
+  if (chunks <= x->chunks_cap) return;
+  x->chunks_cap = 0;
+  dalloc(x->csum, chunks);
+  dalloc(x->cbase, chunks + 1);
+  dalloc(x->csums2, scan_blocks(chunks) + 1);
+  x->chunks_cap = chunks;
+}
+
+int plan_locked(s3imph_index* x, const uint64_t* d_qpos, const int32_t* d_rel, uint64_t nq, int mode, int32_t max_rel,
+                uint64_t min_count, uint64_t min_bytes, int32_t* d_levels, uint64_t* d_row_ptr, uint64_t row_ptr_cap,
+                uint64_t* n_rows, uint64_t* total, hipStream_t s) {
+  const bool upto = mode == S3IMPH_DESC_UPTO, filtered = min_count || min_bytes;
+  const uint64_t R = upto ? std::min<uint64_t>(max_rel > 0 ? (uint64_t)max_rel : 0, x->a.max_depth) : 1;
+  x->have_plan = false;
+  if (nq == 0) {
+    x->have_plan = true;
+    x->plan_rows = x->plan_total_u = x->plan_total = 0;
+    x->plan_filtered = false;
+    return S3IMPH_OK;
+  }
+  if (R && nq > ((1ull << 31) - 1) / R) {
+    x->last_msg = "descendants plan: 2^31 result rows or more in one batch";
+    return S3IMPH_ERR_INVALID;
+  }
+  const uint64_t rows = nq * R;
+  if (row_ptr_cap < rows + 1) {
+    x->last_msg = "descendants plan: row_ptr needs " + std::to_string(rows + 1) + " entries";
+    return S3IMPH_ERR_INVALID;
+  }
+  *n_rows = rows;
+  if (rows == 0) {  // UPTO with no level to return: every query answers nil
+    HIPCHECK(hipMemsetAsync(d_levels, 0, nq * sizeof(int32_t), s));
+    HIPCHECK(hipMemsetAsync(d_row_ptr, 0, sizeof(uint64_t), s));
+    HIPCHECK(hipStreamSynchronize(s));
+    x->have_plan = true;
+    x->plan_rows = x->plan_total_u = x->plan_total = 0;
+    x->plan_filtered = false;
+    return S3IMPH_OK;
+  }
+  ensure_rows(x, rows);
+  k_desc_ranges<<<(unsigned)((rows + kQT - 1) / kQT), kQT, 0, s>>>(x->a, d_qpos, d_rel, rows, upto ? 1 : 0, (uint32_t)R,
+                                                                  max_rel, d_levels, x->row_lo, x->row_len);
+  launch_rows_scan(x->row_len, rows, x->sums, x->U, filtered ? nullptr : d_row_ptr, s);
+  HIPCHECK(hipGetLastError());
+  uint64_t tu = 0;
+  HIPCHECK(hipMemcpyAsync(&tu, x->U + rows, sizeof tu, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  uint64_t tf = tu;
+  if (filtered) {
+    if (tu == 0) {
+      HIPCHECK(hipMemsetAsync(d_row_ptr, 0, (rows + 1) * sizeof(uint64_t), s));
+    } else {
+      const uint64_t chunks = (tu + kChunk - 1) / kChunk;
+      if (chunks + 1 > 0x7fffffffull) {
+        x->last_msg = "descendants plan: more than 2^42 candidates in one batch";
+        return S3IMPH_ERR_INVALID;
+      }
+      ensure_chunks(x, chunks);
+      k_desc_filter<kCount><<<(unsigned)chunks, kChunkT, 0, s>>>(x->a, x->U, x->row_lo, rows, tu, min_count, min_bytes,
+                                                                 x->csum, nullptr, nullptr, nullptr);
+      launch_rows_scan(x->csum, chunks, x->csums2, x->cbase, nullptr, s);
+      k_desc_filter<kRows><<<(unsigned)(tu / kChunk + 1), kChunkT, 0, s>>>(
+          x->a, x->U, x->row_lo, rows, tu, min_count, min_bytes, nullptr, x->cbase, d_row_ptr, nullptr);
+      HIPCHECK(hipGetLastError());
+      HIPCHECK(hipMemcpyAsync(&tf, x->cbase + chunks, sizeof tf, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    if (tu == 0) tf = 0;
+  }
+  *total = tf;
+  x->have_plan = true;
+  x->plan_rows = rows;
+  x->plan_total_u = tu;
+  x->plan_total = tf;
+  x->plan_filtered = filtered;
+  x->plan_mc = min_count;
+  x->plan_mb = min_bytes;
+  return S3IMPH_OK;
+}
+
+}  // namespace
+}  // namespace s3imph
+
+extern "C" {
+
+int s3imph_index_open(int device, const char* dir, s3imph_index** out, char* err, size_t errlen) {
+  if (!out || !dir) {
+    set_err(err, errlen, "invalid argument");
+    return S3IMPH_ERR_INVALID;
+  }
+  *out = nullptr;
+  try {
+    HostIndex h;
+    std::string msg;
+    // all validation on the host, before the device is selected or anything allocated on it
+    const int rc = load_host_index(dir, &h, &msg);
+    if (rc != S3IMPH_OK) {
+      set_err(err, errlen, msg);
+      return rc;
+    }
+    s3imph_index* x = nullptr;
+    try {
+      x = index_new(device, h.mph.data(), h.mph.size(), h.n);
+      HIPCHECK(hipSetDevice(device));
+      x->a.n = h.n;
+      x->a.max_depth = h.max_depth;
+      x->a.send = upload(x, h.send.u64(), h.n);
+      x->a.depth = upload(x, h.depth.u32(), h.n);
+      x->a.mds = upload(x, h.mds.u32(), h.n);
+      x->a.doff = upload(x, h.doff.u64(), h.doff.count);
+      x->a.dpos = upload(x, h.dpos.u64(), h.dpos.count);
+      x->a.fp = upload(x, h.fp.u64(), h.n);
+      x->a.pos = upload(x, h.pos.u64(), h.n);
+      if (h.stats) {
+        x->a.ocnt = upload(x, h.ocnt.u64(), h.n);
+        x->a.tbytes = upload(x, h.tbytes.u64(), h.n);
+      }
+    } catch (const Fail& f) {
+      index_free(x);
+      set_err(err, errlen, f.msg);
+      return f.code;
+    }
+    *out = x;
+    return S3IMPH_OK;
+  } catch (const std::bad_alloc&) {
+    set_err(err, errlen, "open index: out of host memory");
+    return S3IMPH_ERR_NOMEM;
+  }
+}
+
+int s3imph_index_attach(int device, const s3imph_index_arrays* a, s3imph_index** out, char* err, size_t errlen) {
+  if (!out || !a || (a->mph_len && !a->mph_bin) || !a->d_depth_offsets ||
+      (a->n && (!a->d_fp || !a->d_pos || !a->d_depth || !a->d_max_depth_in_subtree || !a->d_subtree_end ||
+                !a->d_depth_positions)) ||
+      (a->d_object_count == nullptr) != (a->d_total_bytes == nullptr) || a->n > 0xffffffffull ||
+      (a->n == 0) != (a->mph_len == 0)) {
+    set_err(err, errlen, "invalid argument");
+    return S3IMPH_ERR_INVALID;
+  }
+  *out = nullptr;
+  try {
+    s3imph_index* x = index_new(device, a->mph_bin, a->mph_len, a->n);
+    x->a.n = a->n;
+    x->a.max_depth = a->max_depth;
+    x->a.fp = a->d_fp;
+    x->a.pos = a->d_pos;
+    x->a.depth = a->d_depth;
+    x->a.mds = a->d_max_depth_in_subtree;
+    x->a.send = a->d_subtree_end;
+    x->a.doff = a->d_depth_offsets;
+    x->a.dpos = a->d_depth_positions;
+    x->a.ocnt = a->d_object_count;
+    x->a.tbytes = a->d_total_bytes;
+    *out = x;
+    return S3IMPH_OK;
+  } catch (const Fail& f) {
+    set_err(err, errlen, f.msg);
+    return f.code;
+  } catch (const std::bad_alloc&) {
+    set_err(err, errlen, "attach index: out of host memory");
+    return S3IMPH_ERR_NOMEM;
+  }
+}
+
+int s3imph_index_close(s3imph_index* x) {
+  index_free(x);
+  return S3IMPH_OK;
+}
+
+uint64_t s3imph_index_count(const s3imph_index* x) { return x ? x->a.n : 0; }
+
+uint64_t s3imph_index_max_depth(const s3imph_index* x) { return x ? x->a.max_depth : 0; }
+
+const char* s3imph_index_last_error(s3imph_index* x) { return x ? x->last_msg.c_str() : ""; }
+
+int s3imph_index_lookup_device(s3imph_index* x, const uint8_t* d_blob, const uint64_t* d_offsets, uint64_t nq,
+                               uint64_t* d_pos_out, void* stream) {
+  if (!x || (nq && (!d_blob || !d_offsets || !d_pos_out))) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(x->mu);
+  x->last_msg.clear();
+  const int rc = s3imph_lookup_device(x->ctx, d_blob, d_offsets, nq, x->a.fp, x->a.pos, x->a.n, d_pos_out, stream);
+  if (rc != S3IMPH_OK) x->last_msg = std::string("lookup: ") + s3imph_status_string(rc);
+  return rc;
+}
+
+int s3imph_index_nodes_device(s3imph_index* x, const uint64_t* d_qpos, uint64_t nq, s3imph_node* d_out, void* stream) {
+  if (!x || (nq && (!d_qpos || !d_out))) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(x->mu);
+  x->last_msg.clear();
+  if (nq == 0) return S3IMPH_OK;
+  try {
+    HIPCHECK(hipSetDevice(x->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+    k_index_nodes<<<(unsigned)((nq + kQT - 1) / kQT), kQT, 0, s>>>(x->a, d_qpos, nq, d_out);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
+    return S3IMPH_OK;
+  } catch (const Fail& f) {
+    x->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+int s3imph_index_descendants_plan(s3imph_index* x, const uint64_t* d_qpos, const int32_t* d_rel, uint64_t nq, int mode,
+                                  int32_t max_rel, uint64_t min_count, uint64_t min_bytes, int32_t* d_levels,
+                                  uint64_t* d_row_ptr, uint64_t row_ptr_cap, uint64_t* n_rows, uint64_t* total,
+                                  void* stream) {
+  if (!x || !n_rows || !total) return S3IMPH_ERR_INVALID;
+  *n_rows = 0;
+  *total = 0;
+  std::lock_guard<std::mutex> lk(x->mu);
+  x->last_msg.clear();
+  const bool filtered = min_count || min_bytes;
+  if ((mode != S3IMPH_DESC_AT && mode != S3IMPH_DESC_UPTO) || (mode == S3IMPH_DESC_UPTO && filtered) ||
+      (nq && (!d_qpos || !d_levels || !d_row_ptr)) || (nq && mode == S3IMPH_DESC_AT && !d_rel)) {
+    x->last_msg = mode == S3IMPH_DESC_UPTO && filtered ? "descendants plan: no filter with DescendantsUpToDepth"
+                                                       : "descendants plan: invalid argument";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (filtered && !x->a.ocnt) {
+    x->last_msg = "descendants plan: the index has no object_count / total_bytes to filter on";
+    return S3IMPH_ERR_STATE;
+  }
+  try {
+    HIPCHECK(hipSetDevice(x->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+    std::string msg;
+    const int rc = retry_on_nomem(x->ctx, s, &msg, [&] {
+      return plan_locked(x, d_qpos, d_rel, nq, mode, max_rel, min_count, min_bytes, d_levels, d_row_ptr, row_ptr_cap,
+                         n_rows, total, s);
+    });
+    if (rc != S3IMPH_OK && x->last_msg.empty()) x->last_msg = msg;
+    return rc;
+  } catch (const Fail& f) {
+    x->have_plan = false;
+    x->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+int s3imph_index_descendants_fill(s3imph_index* x, uint64_t* d_out, uint64_t cap, void* stream) {
+  if (!x) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(x->mu);
+  x->last_msg.clear();
+  if (!x->have_plan) {
+    x->last_msg = "descendants fill: no plan";
+    return S3IMPH_ERR_STATE;
+  }
+  if (cap < x->plan_total || (x->plan_total && !d_out)) {
+    x->last_msg = "descendants fill: out needs " + std::to_string(x->plan_total) + " entries";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (x->plan_total == 0) return S3IMPH_OK;
+  try {
+    HIPCHECK(hipSetDevice(x->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+    const uint64_t tu = x->plan_total_u, chunks = (tu + kChunk - 1) / kChunk;
+    if (chunks > 0x7fffffffull) {
+      x->last_msg = "descendants fill: more than 2^42 positions in one batch";
+      return S3IMPH_ERR_INVALID;
+    }
+    if (x->plan_filtered)
+      k_desc_filter<kFill><<<(unsigned)chunks, kChunkT, 0, s>>>(x->a, x->U, x->row_lo, x->plan_rows, tu, x->plan_mc,
+                                                               x->plan_mb, nullptr, x->cbase, nullptr, d_out);
+    else
+      k_desc_fill<<<(unsigned)chunks, kChunkT, 0, s>>>(x->U, x->row_lo, x->plan_rows, tu, x->a.dpos, d_out);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
+    return S3IMPH_OK;
+  } catch (const Fail& f) {
+    x->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+}  // extern "C"

@@ -11,7 +11,8 @@ Mirrors the reference's MPHF stage interface, ``format.StreamingMPHFBuilder``
     b.close()                                # Close (:105)
 
 plus the device-resident API that bench.py times (``DeviceBuilder``), the
-multi-GPU rank API (``DistBuilder``) and the batched lookup.
+multi-GPU rank API (``DistBuilder``), the batched lookup (``MPHF``) and the reader,
+``Index`` (indexread.Index: Open / Lookup / Stats / Descendants* over a batch).
 
 Every compute call goes through the HIP library; there is no CPU fallback.
 If libs3imph.so is missing, importing this module raises.
@@ -67,6 +68,9 @@ EXPORTS = (
     "s3imph_finalize_index_host", "s3imph_finalize_index_device",
     "s3imph_write_manifest", "s3imph_verify_manifest", "s3imph_sha256_file",
     "s3imph_dev_knobs", "s3imph_build_host_into", "s3imph_mph_bin_bound", "s3imph_release_workspaces",
+    "s3imph_index_open", "s3imph_index_attach", "s3imph_index_close", "s3imph_index_count",
+    "s3imph_index_max_depth", "s3imph_index_last_error", "s3imph_index_lookup_device",
+    "s3imph_index_nodes_device", "s3imph_index_descendants_plan", "s3imph_index_descendants_fill",
 )
 
 
@@ -101,6 +105,25 @@ class BuildInfo(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class IndexArrays(ctypes.Structure):
+    """s3imph_index_arrays: an index's arrays in HBM (include/s3imph.h, section 5c)."""
+    _fields_ = [
+        ("mph_bin", ctypes.c_void_p), ("mph_len", ctypes.c_uint64), ("n", ctypes.c_uint64),
+        ("d_fp", ctypes.c_void_p), ("d_pos", ctypes.c_void_p),
+        ("d_depth", ctypes.c_void_p), ("d_max_depth_in_subtree", ctypes.c_void_p),
+        ("d_subtree_end", ctypes.c_void_p), ("d_depth_offsets", ctypes.c_void_p),
+        ("d_depth_positions", ctypes.c_void_p), ("max_depth", ctypes.c_uint32),
+        ("d_object_count", ctypes.c_void_p), ("d_total_bytes", ctypes.c_void_p),
+    ]
+
+
+# s3imph_node: what Index.nodes returns, one record per queried position
+NODE_DTYPE = np.dtype([("pos", "<u8"), ("subtree_end", "<u8"), ("object_count", "<u8"), ("total_bytes", "<u8"),
+                       ("depth", "<u4"), ("max_depth_in_subtree", "<u4"), ("found", "<u4"), ("pad", "<u4")])
+DESC_AT = 0    # DescendantsAtDepth[Filtered]: one result row per query
+DESC_UPTO = 1  # DescendantsUpToDepth: min(max_rel, maxDepth) result rows per query
 
 
 def _load():
@@ -153,6 +176,17 @@ def _load():
         "s3imph_build_host_into": (i32, [i32, vp, vp, vp, u64, vp, vp, vp, u64, P(u64), cp, sz]),
         "s3imph_mph_bin_bound": (u64, [u64]),
         "s3imph_release_workspaces": (i32, []),
+        "s3imph_index_open": (i32, [i32, cp, P(vp), cp, sz]),
+        "s3imph_index_attach": (i32, [i32, P(IndexArrays), P(vp), cp, sz]),
+        "s3imph_index_close": (i32, [vp]),
+        "s3imph_index_count": (u64, [vp]),
+        "s3imph_index_max_depth": (u64, [vp]),
+        "s3imph_index_last_error": (cp, [vp]),
+        "s3imph_index_lookup_device": (i32, [vp, vp, vp, u64, vp, vp]),
+        "s3imph_index_nodes_device": (i32, [vp, vp, u64, vp, vp]),
+        "s3imph_index_descendants_plan": (i32, [vp, vp, vp, u64, i32, ctypes.c_int32, u64, u64, vp, vp, u64,
+                                                P(u64), P(u64), vp]),
+        "s3imph_index_descendants_fill": (i32, [vp, vp, u64, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -586,6 +620,229 @@ class MPHF:
 
     def close(self) -> None:
         self.ctx.close()
+
+
+class Index:
+    """indexread.Index on the GPU (pkg/indexread/index.go; include/s3imph.h section 5c): the
+    index's arrays in HBM and the reader's queries answered for a whole batch per call.
+
+        idx = Index(dir)                          # Open (:31)
+        idx.count, idx.max_depth                  # Count (:188), MaxDepth (:193)
+        idx.lookup(keys)                          # Lookup (:128), 2^64-1 when not found
+        idx.nodes(pos)                            # Stats / Depth / SubtreeEnd / MaxDepthInSubtree (:135-176)
+        idx.stats_for_prefix(keys)                # StatsForPrefix (:146)
+        idx.descendants_at_depth(pos, rel)        # DescendantsAtDepth[Filtered] (:206, :277)
+        idx.descendants_up_to_depth(pos, max_rel) # DescendantsUpToDepth (:239)
+        idx.prefix_string(pos)                    # PrefixString (:179)
+        idx.close()                               # Close (:108)
+
+    Positions are given as a sequence, a numpy array or a device tensor (int64 holding the
+    u64 bits).  object_count.u64 / total_bytes.u64 are optional (zeros without them)."""
+
+    def __init__(self, dir_: str, device: int = 0):
+        err = ctypes.create_string_buffer(1024)
+        h = ctypes.c_void_p()
+        _check(LIB.s3imph_index_open(device, os.fsencode(dir_), ctypes.byref(h), err, 1024), err)
+        self._h = h
+        self._init(device, dir_, None)
+
+    def _init(self, device: int, dir_: str | None, keep) -> None:
+        self.device = device
+        self.dev = f"cuda:{device}"
+        self.dir = dir_
+        self._keep = keep  # borrowed device tensors stay alive with the handle
+        self._prefixes = None
+        self.count = int(LIB.s3imph_index_count(self._h))
+        self.max_depth = int(LIB.s3imph_index_max_depth(self._h))
+
+    @classmethod
+    def from_arrays(cls, mph_bin: bytes, fp, pos, depth, subtree_end, max_depth_in_subtree, depth_offsets,
+                    depth_positions, max_depth: int | None = None, object_count=None, total_bytes=None,
+                    device: int | None = None) -> "Index":
+        """s3imph_index_attach: an index over device tensors (e.g. DeviceBuilder.build's outputs,
+        mph_bin() and finalize_index()'s arrays), borrowed for the life of the handle."""
+        if device is None:
+            device = fp.device.index or 0
+        n = int(fp.shape[0])
+        a = IndexArrays()
+        buf = ctypes.create_string_buffer(mph_bin, max(len(mph_bin), 1))
+        a.mph_bin, a.mph_len, a.n = ctypes.cast(buf, ctypes.c_void_p).value, len(mph_bin), n
+        a.d_fp, a.d_pos = fp.data_ptr(), pos.data_ptr()
+        a.d_depth, a.d_max_depth_in_subtree = depth.data_ptr(), max_depth_in_subtree.data_ptr()
+        a.d_subtree_end, a.d_depth_offsets = subtree_end.data_ptr(), depth_offsets.data_ptr()
+        a.d_depth_positions = depth_positions.data_ptr()
+        a.max_depth = int(depth_offsets.shape[0]) - 2 if max_depth is None else max_depth
+        a.d_object_count = None if object_count is None else object_count.data_ptr()
+        a.d_total_bytes = None if total_bytes is None else total_bytes.data_ptr()
+        err = ctypes.create_string_buffer(1024)
+        h = ctypes.c_void_p()
+        _check(LIB.s3imph_index_attach(device, ctypes.byref(a), ctypes.byref(h), err, 1024), err)
+        self = cls.__new__(cls)
+        self._h = h
+        self._init(device, None, (fp, pos, depth, subtree_end, max_depth_in_subtree, depth_offsets, depth_positions,
+                                  object_count, total_bytes))
+        return self
+
+    def last_error(self) -> str:
+        return LIB.s3imph_index_last_error(self._h).decode(errors="replace")
+
+    def _fail(self, rc: int, what: str):
+        if rc != OK:
+            raise MPHFError(rc, f"{what}: {self.last_error() or status_string(rc)}")
+
+    def _pos_dev(self, pos):
+        """Query positions as a contiguous int64 device tensor (u64 bits)."""
+        import torch
+        if torch.is_tensor(pos):
+            return pos.to(device=self.dev, dtype=torch.int64).contiguous()
+        a = np.ascontiguousarray(np.asarray(pos, dtype=np.uint64).reshape(-1))
+        return torch.from_numpy(a.view(np.int64).copy()).to(self.dev)
+
+    # -- Lookup ------------------------------------------------------------------------
+    def lookup_device(self, d_blob, d_offsets, nq: int, stream=None):
+        """s3imph_index_lookup_device over a query blob in HBM: an int64 tensor of u64 positions."""
+        import torch
+        res = torch.empty(max(nq, 1), dtype=torch.int64, device=self.dev)
+        self._fail(LIB.s3imph_index_lookup_device(self._h, _dev_ptr(d_blob), _dev_ptr(d_offsets), nq, _dev_ptr(res),
+                                                  _stream_ptr(stream)), "lookup")
+        return res[:nq]
+
+    def _keys_dev(self, blob: np.ndarray, offsets: np.ndarray):
+        """A query blob (padded to whole words) and its offsets on the device, and the key count."""
+        import torch
+        pad = np.zeros(((len(blob) + 7) // 8) * 8 + 8, np.uint8)
+        pad[:len(blob)] = blob
+        d_offs = torch.from_numpy(np.array(offsets, dtype=np.uint64).view(np.int64)).to(self.dev)
+        return torch.from_numpy(pad).to(self.dev), d_offs, len(offsets) - 1
+
+    def lookup_blob(self, blob: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+        return self.lookup_device(*self._keys_dev(blob, offsets)).cpu().numpy().view(np.uint64)
+
+    def lookup(self, keys) -> np.ndarray:
+        """Lookup (index.go:128) of a batch: pos per key, or 2^64-1 when not found."""
+        return self.lookup_blob(*keys_to_blob(keys))
+
+    # -- Stats / Depth / SubtreeEnd / MaxDepthInSubtree --------------------------------
+    def nodes_device(self, pos, stream=None):
+        """s3imph_index_nodes_device: an (nq, 6) int64 tensor holding one s3imph_node per row."""
+        import torch
+        d_pos = self._pos_dev(pos)
+        nq = int(d_pos.shape[0])
+        out = torch.empty((max(nq, 1), NODE_DTYPE.itemsize // 8), dtype=torch.int64, device=self.dev)
+        self._fail(LIB.s3imph_index_nodes_device(self._h, _dev_ptr(d_pos), nq, _dev_ptr(out), _stream_ptr(stream)),
+                   "nodes")
+        return out[:nq]
+
+    def nodes(self, pos) -> np.ndarray:
+        """One NODE_DTYPE record per position; all zero with found = 0 when pos >= count."""
+        t = self.nodes_device(pos)
+        if t.shape[0] == 0:
+            return np.zeros(0, NODE_DTYPE)
+        return t.cpu().numpy().reshape(-1).view(NODE_DTYPE)
+
+    def stats_for_prefix(self, keys):
+        """StatsForPrefix (index.go:146): (found bool, object_count u64, total_bytes u64) arrays."""
+        blob, offs = keys_to_blob(keys)
+        return self.stats_for_prefix_blob(blob, offs)
+
+    def stats_for_prefix_blob(self, blob: np.ndarray, offsets: np.ndarray):
+        r = self.nodes(self.lookup_device(*self._keys_dev(blob, offsets)))
+        return r["found"] != 0, r["object_count"].copy(), r["total_bytes"].copy()
+
+    # -- Descendants -------------------------------------------------------------------
+    def descendants_plan(self, pos, rel=None, max_rel: int = 0, min_count: int = 0, min_bytes: int = 0,
+                         row_ptr_cap: int | None = None, stream=None):
+        """s3imph_index_descendants_plan.  rel given (an int for the batch or one per query):
+        DESC_AT; rel None: DESC_UPTO with max_rel.  Returns (levels int32[nq], row_ptr
+        int64[n_rows + 1], n_rows, total), tensors on the device."""
+        import torch
+        d_pos = self._pos_dev(pos)
+        nq = int(d_pos.shape[0])
+        if rel is not None:
+            mode, rows = DESC_AT, nq
+            if torch.is_tensor(rel):
+                d_rel = rel.to(device=self.dev, dtype=torch.int32).contiguous()
+            else:
+                d_rel = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(rel, np.int32), (nq,)))
+                                         .copy()).to(self.dev)
+        else:
+            mode, rows, d_rel = DESC_UPTO, nq * min(max(max_rel, 0), self.max_depth), None
+        cap = rows + 1 if row_ptr_cap is None else row_ptr_cap
+        levels = torch.empty(max(nq, 1), dtype=torch.int32, device=self.dev)
+        row_ptr = torch.zeros(max(cap, 1), dtype=torch.int64, device=self.dev)
+        n_rows, total = ctypes.c_uint64(), ctypes.c_uint64()
+        self._fail(LIB.s3imph_index_descendants_plan(self._h, _dev_ptr(d_pos), _dev_ptr(d_rel), nq, mode, max_rel,
+                                                     min_count, min_bytes, _dev_ptr(levels), _dev_ptr(row_ptr), cap,
+                                                     ctypes.byref(n_rows), ctypes.byref(total), _stream_ptr(stream)),
+                   "descendants plan")
+        return levels[:nq], row_ptr[: n_rows.value + 1], int(n_rows.value), int(total.value)
+
+    def descendants_fill(self, total: int, cap: int | None = None, stream=None):
+        """s3imph_index_descendants_fill of the last plan: an int64 tensor of `total` u64 positions."""
+        import torch
+        cap = total if cap is None else cap
+        out = torch.empty(max(cap, 1), dtype=torch.int64, device=self.dev)
+        self._fail(LIB.s3imph_index_descendants_fill(self._h, _dev_ptr(out), cap, _stream_ptr(stream)),
+                   "descendants fill")
+        return out[:total]
+
+    def descendants_csr(self, pos, rel=None, max_rel: int = 0, min_count: int = 0, min_bytes: int = 0, stream=None):
+        """The raw form: (levels, row_ptr, out) tensors on the device.  Row r of the batch is
+        out[row_ptr[r] : row_ptr[r + 1]]; DESC_AT has one row per query, DESC_UPTO
+        min(max(max_rel, 0), max_depth) rows per query of which the first levels[q] count."""
+        levels, row_ptr, _, total = self.descendants_plan(pos, rel, max_rel, min_count, min_bytes, stream=stream)
+        return levels, row_ptr, self.descendants_fill(total, stream=stream)
+
+    def descendants_at_depth(self, pos, rel, min_count: int = 0, min_bytes: int = 0) -> list:
+        """DescendantsAtDepth / DescendantsAtDepthFiltered (index.go:206, :277) per query: None
+        where the reference returns nil, else the u64 positions (possibly none)."""
+        levels, row_ptr, out = self.descendants_csr(pos, rel, 0, min_count, min_bytes)
+        lv, rp = levels.cpu().numpy(), row_ptr.cpu().numpy()
+        o = out.cpu().numpy().view(np.uint64)
+        return [o[rp[q]:rp[q + 1]] if lv[q] else None for q in range(len(lv))]
+
+    def descendants_up_to_depth(self, pos, max_rel: int) -> list:
+        """DescendantsUpToDepth (index.go:239) per query: None where the reference returns nil,
+        else one u64 array per depth level."""
+        levels, row_ptr, out = self.descendants_csr(pos, None, max_rel)
+        lv, rp = levels.cpu().numpy(), row_ptr.cpu().numpy()
+        o = out.cpu().numpy().view(np.uint64)
+        R = (len(rp) - 1) // len(lv) if len(lv) else 0
+        return [[o[rp[q * R + j]:rp[q * R + j + 1]] for j in range(lv[q])] if lv[q] else None
+                for q in range(len(lv))]
+
+    # -- PrefixString ------------------------------------------------------------------
+    def prefix_string(self, pos: int) -> str:
+        """PrefixString (index.go:179) from prefix_blob.bin / prefix_offsets.u64."""
+        if self._prefixes is None:
+            bp = None if self.dir is None else os.path.join(self.dir, "prefix_blob.bin")
+            if bp is None or not os.path.exists(bp):
+                raise MPHFError(ERR_STATE, f"get prefix for pos {pos}: prefix blob not loaded")
+            offs = read_u64_array(os.path.join(self.dir, "prefix_offsets.u64"))
+            self._prefixes = (np.memmap(bp, dtype=np.uint8, mode="r") if os.path.getsize(bp) else
+                              np.zeros(0, np.uint8), offs)
+        blob, offs = self._prefixes
+        if pos < 0 or pos + 1 >= len(offs):
+            raise MPHFError(ERR_INVALID, f"get prefix for pos {pos}: position out of bounds")
+        return bytes(blob[int(offs[pos]):int(offs[pos + 1])]).decode(errors="surrogateescape")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            LIB.s3imph_index_close(self._h)
+            self._h = None
+            self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def dist_unique_id() -> bytes:
