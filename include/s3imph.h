@@ -347,8 +347,8 @@ int s3imph_sha256_file(const char *path, int portable, char hex_out[65], char *e
  *
  *     Differences from the reference's Open, both deliberate:
  *       - object_count.u64 and total_bytes.u64 are optional (Open requires them,
- *         index.go:46-56): this project's pipeline does not write them, they are the
- *         caller's aggregation data.  Without them object_count / total_bytes read 0 and
+ *         index.go:46-56): only s3imph_index_from_objects_host (section 5d) writes them, the
+ *         other builds leave them to the caller's aggregation.  Without them object_count / total_bytes read 0 and
  *         a non-zero filter returns S3IMPH_ERR_STATE.  Tier stats are out of scope.
  *       - Open validates the values, not only the headers (the reference trusts the
  *         files): see s3imph_index_open.  No kernel is ever handed an index that could
@@ -442,6 +442,71 @@ int s3imph_index_descendants_plan(s3imph_index *idx, const uint64_t *d_qpos, con
                                   int32_t *d_levels /* nq */, uint64_t *d_row_ptr /* n_rows + 1 */,
                                   uint64_t row_ptr_cap, uint64_t *n_rows, uint64_t *total, void *stream);
 int s3imph_index_descendants_fill(s3imph_index *idx, uint64_t *d_out, uint64_t cap, void *stream);
+
+/* ------------------------------------------------------------------------
+ * 5d. extsort.Aggregator + SortPrefixRows (pkg/extsort/aggregator.go:44-76, :138-) on the
+ *     GPU: a byte-sorted object listing (keys in the blob / offsets layout, one size per key)
+ *     becomes the prefix rows IndexBuilder.Add consumes (indexbuild.go:154-199) — prefix
+ *     bytes, depth, object count, total bytes — in the reference's sorted order, and from
+ *     there a whole index directory.  The keys must be in non-decreasing byte order (equal
+ *     neighbours allowed); the key blob on the device is readable up to round_up(offsets[m], 8)
+ *     and may have any byte alignment.  max_depth is NewAggregator's maxDepth (aggregator.go:25,
+ *     :53): 0 = unlimited.  Row 0 is the root "" (aggregator.go:48) with every object; m == 0
+ *     gives no rows (Drain returns nil).  Sums wrap like Go's uint64 +=.  The per-tier columns
+ *     (TierCounts / TierBytes) are out of scope: the reader does not read them (section 5c).
+ * ------------------------------------------------------------------------ */
+typedef struct s3imph_agg_info {
+    uint64_t n_prefixes;      /* rows, the root included */
+    uint64_t blob_bytes;      /* bytes of all prefixes (prefix_blob.bin's size) */
+    uint64_t n_objects;       /* m: Aggregator.ObjectCount (aggregator.go:84) */
+    uint64_t total_bytes;     /* sum of the sizes mod 2^64: BytesProcessed (aggregator.go:89) */
+    uint64_t first_unsorted;  /* smallest i with key[i] < key[i-1]; UINT64_MAX when sorted */
+    uint32_t max_depth_seen;  /* deepest row depth (after the max_depth cut) */
+    uint32_t pad;
+} s3imph_agg_info;
+
+/* AddObject over the whole listing (aggregator.go:44-61), first half: one pass over the keys
+ * and the scans that size the result; fills *info.  d_sizes NULL: every size is 0.
+ * S3IMPH_ERR_INVALID (message: s3imph_ctx_last_error) when the keys are not sorted
+ * (info->first_unsorted holds the index), when a key has more than 65535 '/' within
+ * max_depth (PrefixRow.Depth is a uint16, aggregator.go:50: refused, not wrapped), or when
+ * there are more than 2^30 rows (s3imph_build_device could not take them).  m == 0 is OK with
+ * zero rows.  The key arrays must stay valid and unchanged until the fill that follows; a
+ * later plan replaces the earlier one.  The scratch lives in ctx and grows on demand.
+ * Synchronous on `stream`. */
+int s3imph_aggregate_plan_device(s3imph_ctx *ctx, const uint8_t *d_keys, const uint64_t *d_key_offsets,
+                                 const uint64_t *d_sizes, uint64_t m, uint32_t max_depth,
+                                 s3imph_agg_info *info, void *stream);
+
+/* Drain + SortPrefixRows (aggregator.go:138-): writes the rows of the last plan in byte order —
+ * d_blob (blob_cap >= round_up(blob_bytes, 8) bytes; the padding is written as zeros, so the
+ * result goes straight into s3imph_build_device), d_offsets (n_prefixes + 1 entries), and
+ * n_cap >= n_prefixes entries each of d_depth (PrefixRow.Depth), d_object_count (Count) and
+ * d_total_bytes (TotalBytes).  S3IMPH_ERR_STATE without a plan, S3IMPH_ERR_INVALID when a
+ * capacity is short.  Synchronous on `stream`. */
+int s3imph_aggregate_fill_device(s3imph_ctx *ctx, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offsets,
+                                 uint32_t *d_depth, uint64_t *d_object_count, uint64_t *d_total_bytes,
+                                 uint64_t n_cap, void *stream);
+
+/* The same from host memory (H2D, plan, fill, D2H): replaces the AddObject loop + Drain
+ * (aggregator.go:44-61, :138-).  The five arrays are allocated by the library (release each
+ * with s3imph_free); *n = rows.  m == 0: *n = 0, *offsets = [0], the others NULL. */
+int s3imph_aggregate_host(int device, const uint8_t *keys, const uint64_t *key_offsets, const uint64_t *sizes,
+                          uint64_t m, uint32_t max_depth, uint8_t **blob, uint64_t **offsets, uint32_t **depth,
+                          uint64_t **object_count, uint64_t **total_bytes, uint64_t *n, char *err,
+                          size_t errlen);
+
+/* Object listing in, index directory out, in one device residency: replaces Aggregator +
+ * SortPrefixRows + the IndexBuilder.Add loop + Finalize (indexbuild.go:154-199, :393-432).
+ * Aggregates, runs s3imph_build_device on the produced blob and s3imph_finalize_index_device
+ * with the produced depths, then writes the five MPHF-stage files, the five finalize files,
+ * object_count.u64 / total_bytes.u64 (S3ID u64 arrays, the ArrayWriters of indexbuild.go:179-184)
+ * and manifest.json.  The rows visit the host only to be written.  m == 0 writes the empty
+ * index s3imph_index_open accepts.  Error texts are wrapped like the reference's
+ * ("aggregate: ...", "build MPHF: ..."); the out-of-memory retry of the host builds applies. */
+int s3imph_index_from_objects_host(int device, const uint8_t *keys, const uint64_t *key_offsets,
+                                   const uint64_t *sizes, uint64_t m, uint32_t max_depth, const char *out_dir,
+                                   char *err, size_t errlen);
 
 /* ------------------------------------------------------------------------
  * 6. Deterministic synthetic prefix sets (bench/test support, not on the path).

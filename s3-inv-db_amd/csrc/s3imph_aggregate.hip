@@ -1,0 +1,855 @@
+// s3imph_aggregate.hip — the front of the pipeline on the GPU: a byte-sorted object listing
+// (keys + sizes) in HBM becomes the prefix rows IndexBuilder.Add consumes, and from there a
+// whole index directory (include/s3imph.h section 5d).
+//
+// Reference (pkg/extsort):
+//   aggregator.go:44-76    AddObject: one accumulate("", 0) for the root and one per '/' of
+//                          the key (prefix = key[:i+1], depth = ordinal of that '/'), cut at
+//                          maxDepth when it is > 0; PrefixStats.Add sums count and bytes
+//                          (uint64 +=, wrapping);
+//   aggregator.go:138-     Drain: nil for no prefixes, else the rows sorted by prefix bytes;
+//   indexbuild.go:154-199  IndexBuilder.Add: the consumer of the rows (prefix, depth, count,
+//                          bytes), object_count.u64 / total_bytes.u64 written at :179-184.
+//
+// GPU formulation.  Keys k[0..m) are byte-sorted.  Per key: s = its number
+// of '/', c = the number of '/' inside the longest common prefix with its predecessor
+// (c[0] = 0), both capped at maxDepth.  Key i opens the rows of depths c'+1 .. s' — every
+// shallower prefix was opened by an earlier key — and in that order the rows are already
+// byte-sorted.  The row (i, d) covers the keys [i, e) where e is the first index > i with
+// c[e] < d (or m): count = e - i, bytes = Z[e] - Z[i] over the wrapping prefix sum Z of the
+// sizes.  One pass over the key bytes computes s, c, the row count and the row bytes of
+// each key (with block / superblock minima of c beside it); three scans turn them into row
+// bases, row byte bases and Z; the emit is partitioned by output rows and output bytes,
+// not by key, so a key of thousands of '/' is spread over as many lanes.
+#include <rocprim/device/device_scan.hpp>
+
+#include <sys/stat.h>
+
+#include <cstdlib>
+#include <cstring>
+
+#include "s3imph_ctx.h"
+#include "s3imph_device.h"
+
+namespace s3imph {
+
+s3imph_ctx* default_ctx(int device, std::string* msg);
+int write_finalize_files(const std::string& dir, const uint32_t* depth, const uint64_t* subtree_end,
+                         const uint32_t* max_depth_sub, const uint64_t* depth_offsets, uint64_t n_offsets,
+                         const uint64_t* depth_positions, uint64_t n, std::string* msg);
+int write_stats_files(const std::string& dir, const uint64_t* object_count, const uint64_t* total_bytes, uint64_t n,
+                      std::string* msg);
+int write_manifest(const std::string& dir, uint64_t node_count, uint32_t max_depth, std::string* msg);
+
+namespace {
+
+constexpr int kAB = 1024;  // keys per block (one block minimum of c)
+constexpr int kAS = 1024;  // blocks per superblock
+constexpr int kAT = 256;   // lanes per workgroup of the emit kernels: one row / one blob word each
+constexpr uint64_t kMaxRows = 1ull << 30;  // what the MPHF build takes on one GPU
+constexpr uint32_t kMaxDepth16 = 65535;    // PrefixRow.Depth is a uint16
+
+// What the key pass reports: the smallest unsorted index, the smallest index of a key deeper
+// than a uint16 depth, the deepest (capped) depth.
+struct AggTop {
+  unsigned long long first_unsorted, first_deep;
+  unsigned maxd, pad;
+};
+
+// 8 key bytes from blob address a (any alignment); the blob is readable up to end8 =
+// round_up(offsets[m], 8).  (As in s3imph_finalize.hip.)
+__device__ __forceinline__ uint64_t load8(const uint8_t* blob, uint64_t a, uint64_t end8) {
+  const uint64_t al = a & ~7ull;
+  const uint64_t* w = reinterpret_cast<const uint64_t*>(blob + al);
+  const uint64_t lo = w[0];
+  const uint64_t hi = (a & 7) && al + 8 < end8 ? w[1] : 0;
+  return (a & 7) ? funnel_bytes(lo, hi, (unsigned)(a & 7)) : lo;
+}
+
+// bit 8j+7 set iff byte j of the first `valid` (1..8) bytes of x is '/'
+__device__ __forceinline__ uint64_t slash_bits(uint64_t x, uint64_t valid) {
+  constexpr uint64_t k7f = 0x7f7f7f7f7f7f7f7full;
+  x ^= 0x2f2f2f2f2f2f2f2full;
+  const uint64_t t = (x & k7f) + k7f;
+  uint64_t z = ~(t | x | k7f);
+  if (valid < 8) z &= (1ull << (8 * valid)) - 1;
+  return z;
+}
+
+// First index in [lo, hi) with U[index] > u, or hi.
+__device__ __forceinline__ uint64_t first_above(const uint64_t* __restrict__ U, uint64_t lo, uint64_t hi,
+                                                uint64_t u) {
+  uint64_t len = hi - lo;
+  while (len) {
+    const uint64_t h = len >> 1;
+    const bool right = U[lo + h] <= u;
+    lo = right ? lo + h + 1 : lo;
+    len = right ? len - h - 1 : h;
+  }
+  return lo;
+}
+
+// Key pass: per key i its '/' count s and the '/' count c inside the common prefix with key
+// i - 1, found in one walk over the key's words against its predecessor's; the sortedness
+// check k[i-1] <= k[i] falls out of the same comparison.  Writes c[i], rows[i] = s' - c' and
+// rbytes[i] = the bytes of those rows (the sum of their lengths), the block minimum of c.
+__global__ __launch_bounds__(kAB) void k_agg_keys(const uint8_t* __restrict__ blob,
+                                                  const uint64_t* __restrict__ offsets, uint64_t m, uint32_t cap,
+                                                  uint32_t* __restrict__ c_out, uint64_t* __restrict__ rows,
+                                                  uint64_t* __restrict__ rbytes, uint32_t* __restrict__ bmin,
+                                                  AggTop* __restrict__ top) {
+  __shared__ uint32_t s_min[kAB / 64];
+  __shared__ uint32_t s_max[kAB / 64];
+  const uint64_t i = (uint64_t)blockIdx.x * kAB + threadIdx.x;
+  const uint64_t end8 = (offsets[m] + 7) & ~7ull;
+  uint32_t cmin = 0xffffffffu;  // neutral for the block minimum
+  uint32_t sp = 0;
+  if (i < m) {
+    const uint64_t b0 = offsets[i], len = offsets[i + 1] - b0;
+    const bool cmp = i > 0;
+    const uint64_t p0 = cmp ? offsets[i - 1] : 0, plen = cmp ? b0 - p0 : 0;
+    const uint64_t mm = min(len, plen);  // bytes both keys have
+    bool diverged = !cmp;                // the common prefix has ended
+    bool full = true;                    // ... and it covers all mm bytes
+    bool less = false;                   // k[i] < k[i-1]
+    uint32_t s = 0, cc = 0;
+    uint64_t rb = 0;
+    for (uint64_t k = 0; k < len; k += 8) {
+      const uint64_t w = load8(blob, b0 + k, end8);
+      const uint64_t z = slash_bits(w, len - k) & 0x8080808080808080ull;
+      unsigned nd = 0;  // bytes of this word inside the common prefix
+      if (!diverged) {
+        if (k >= mm) {
+          diverged = true;
+        } else {
+          const uint64_t pw = load8(blob, p0 + k, end8);
+          const uint64_t x = w ^ pw;
+          const unsigned avail = (unsigned)min((uint64_t)8, mm - k);
+          const unsigned fd = x ? (unsigned)(__builtin_ctzll(x) >> 3) : 8u;
+          if (fd < avail) {
+            nd = fd;
+            diverged = true;
+            full = false;
+            less = ((w >> (8 * fd)) & 0xff) < ((pw >> (8 * fd)) & 0xff);
+          } else {
+            nd = avail;
+            diverged = avail < 8;
+          }
+        }
+      }
+      const uint64_t cm = nd >= 8 ? ~0ull : (1ull << (8 * nd)) - 1;
+      const uint32_t inc = (uint32_t)__popcll(z & cm);
+      s += inc;
+      cc += inc;
+      uint64_t zr = z & ~cm;  // the '/' past the common prefix: each opens a row (up to the cap)
+      while (zr) {
+        const unsigned j = (unsigned)(__builtin_ctzll(zr) >> 3);
+        zr &= zr - 1;
+        ++s;
+        if (s <= cap) rb += k + j + 1;
+      }
+    }
+    if (cmp && full && len < plen) less = true;  // a proper prefix of its predecessor
+    sp = min(s, cap);
+    const uint32_t cp = min(cc, cap);
+    if (less) atomicMin(&top->first_unsorted, (unsigned long long)i);
+    if (sp > kMaxDepth16) atomicMin(&top->first_deep, (unsigned long long)i);
+    c_out[i] = cc;
+    rows[i] = sp - cp;
+    rbytes[i] = rb;
+    cmin = cc;
+  }
+  uint32_t mn = cmin, mx = sp;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    mn = min(mn, __shfl_xor(mn, o));
+    mx = max(mx, __shfl_xor(mx, o));
+  }
+  if (lane_id() == 0) {
+    s_min[threadIdx.x >> 6] = mn;
+    s_max[threadIdx.x >> 6] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 0; w < kAB / 64; ++w) {
+      mn = min(mn, s_min[w]);
+      mx = max(mx, s_max[w]);
+    }
+    bmin[blockIdx.x] = mn;
+    if (mx) atomicMax(&top->maxd, mx);
+  }
+}
+
+// Superblock minima of c over the block minima (one workgroup per superblock).
+__global__ __launch_bounds__(kAS) void k_agg_super(const uint32_t* __restrict__ bmin, uint64_t nb,
+                                                   uint32_t* __restrict__ smin) {
+  __shared__ uint32_t s_min[kAS / 64];
+  const uint64_t b = (uint64_t)blockIdx.x * kAS + threadIdx.x;
+  uint32_t mn = b < nb ? bmin[b] : 0xffffffffu;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) mn = min(mn, __shfl_xor(mn, o));
+  if (lane_id() == 0) s_min[threadIdx.x >> 6] = mn;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 0; w < kAS / 64; ++w) mn = min(mn, s_min[w]);
+    smin[blockIdx.x] = mn;
+  }
+}
+
+// The emit kernels cut their output into chunks of kAT units (rows, or 8-byte words of the
+// blob) and need the owner (key, or row) of each chunk's first unit: an upper-bound search in a
+// scan U (entries `entries`) per chunk.  Done here with one lane per chunk, so the searches'
+// dependent loads overlap across chunks instead of standing at the head of every workgroup.
+// out[t] = last index with U[index] <= max(t * step, first_min).
+__global__ __launch_bounds__(kAT) void k_agg_bounds(const uint64_t* __restrict__ U, uint64_t entries, uint64_t step,
+                                                    uint64_t first_min, uint64_t nchunks,
+                                                    uint64_t* __restrict__ out) {
+  const uint64_t t = (uint64_t)blockIdx.x * kAT + threadIdx.x;
+  if (t < nchunks) out[t] = first_above(U, 0, entries, max(t * step, first_min)) - 1;
+}
+
+// Emit, by output row: row r > 0 belongs to the key i with rowbase[i] <= r < rowbase[i+1]
+// (upper-bound search inside the workgroup's keys, k_agg_bounds) and has depth d = c'[i] + 1 +
+// (r - rowbase[i]).  A walk over the key finds its d-th '/' and the bytes of the key's
+// earlier rows; the range end e = first index > i with c[e] < d comes from the element ->
+// block -> superblock -> back down walk of k_fin_subtree.  Row 0 is the root.
+__global__ __launch_bounds__(kAT) void k_agg_rows(const uint8_t* __restrict__ blob,
+                                                  const uint64_t* __restrict__ koff, uint64_t m, uint32_t cap,
+                                                  const uint32_t* __restrict__ c, const uint64_t* __restrict__ rowbase,
+                                                  const uint64_t* __restrict__ keybytes,
+                                                  const uint64_t* __restrict__ bounds,
+                                                  const uint64_t* __restrict__ Z, const uint32_t* __restrict__ bmin,
+                                                  const uint32_t* __restrict__ smin, uint64_t nb, uint64_t nsb,
+                                                  uint64_t n, uint64_t blob_bytes, uint64_t* __restrict__ offsets,
+                                                  uint32_t* __restrict__ depth, uint64_t* __restrict__ ocnt,
+                                                  uint64_t* __restrict__ tbytes, uint64_t* __restrict__ rowsrc) {
+  const uint64_t base = (uint64_t)blockIdx.x * kAT;
+  if (base >= n) return;
+  const uint64_t end = min(n, base + kAT);
+  const uint64_t r = base + threadIdx.x;
+  if (r == 0) {
+    offsets[0] = 0;
+    offsets[n] = blob_bytes;
+    depth[0] = 0;
+    ocnt[0] = m;
+    tbytes[0] = Z ? Z[m] : 0;
+    rowsrc[0] = 0;
+  }
+  if (end < 2) return;  // the root alone
+  // the keys this workgroup's rows come from (rowbase has m + 1 entries, rowbase[0] = 1,
+  // rowbase[m] = n): from the key of its first row to the key of the next workgroup's
+  const uint64_t k_lo = bounds[blockIdx.x];
+  const uint64_t k_hi = blockIdx.x + 1 < gridDim.x ? bounds[blockIdx.x + 1] : m - 1;
+  if (r == 0 || r >= end) return;
+  const uint64_t i = first_above(rowbase, k_lo + 1, k_hi + 1, r) - 1;
+  const uint32_t cp = min(c[i], cap);
+  const uint32_t d = cp + (uint32_t)(r - rowbase[i]) + 1;
+  // the d-th '/' of key i, and the lengths of the key's rows before this one
+  const uint64_t b0 = koff[i], len = koff[i + 1] - b0;
+  const uint64_t end8 = (koff[m] + 7) & ~7ull;
+  uint64_t acc = 0;
+  uint32_t s = 0;
+  for (uint64_t k = 0; k < len; k += 8) {
+    uint64_t z = slash_bits(load8(blob, b0 + k, end8), len - k) & 0x8080808080808080ull;
+    const uint32_t cnt = (uint32_t)__popcll(z);
+    if (s + cnt <= cp) {
+      s += cnt;
+      continue;
+    }
+    bool hit = false;
+    while (z) {
+      const unsigned j = (unsigned)(__builtin_ctzll(z) >> 3);
+      z &= z - 1;
+      ++s;
+      if (s == d) {
+        hit = true;
+        break;
+      }
+      if (s > cp) acc += k + j + 1;
+    }
+    if (hit) break;
+  }
+  offsets[r] = keybytes[i] + acc;
+  rowsrc[r] = b0;
+  depth[r] = d;
+  // e = first index > i with c[e] < d, or m
+  auto scan = [&](uint64_t lo, uint64_t hi) -> uint64_t {
+    for (uint64_t t = lo; t < hi; ++t)
+      if (c[t] < d) return t;
+    return hi;
+  };
+  const uint64_t b = i / kAB;
+  const uint64_t bl_end = min(m, (b + 1) * kAB);
+  uint64_t e = scan(i + 1, bl_end);
+  if (e == bl_end && bl_end < m) {
+    const uint64_t sb = b / kAS;
+    const uint64_t bend = min(nb, (sb + 1) * kAS);
+    uint64_t bb = b + 1;
+    while (bb < bend && bmin[bb] >= d) ++bb;
+    bool none = false;
+    if (bb == bend) {
+      uint64_t q = sb + 1;
+      while (q < nsb && smin[q] >= d) ++q;
+      if (q >= nsb) {
+        none = true;
+      } else {
+        bb = q * kAS;  // smin[q] < d: one of its blocks is below d
+        while (bmin[bb] >= d) ++bb;
+      }
+    }
+    e = none ? m : scan(bb * kAB, min(m, (bb + 1) * kAB));
+  }
+  ocnt[r] = e - i;
+  tbytes[r] = Z ? Z[e] - Z[i] : 0;
+}
+
+// Emit, by output bytes: each lane assembles one 8-byte word of prefix_blob.  The row of a byte
+// is the last one that starts at or before it (upper-bound search in the row offsets inside
+// the workgroup's rows, k_agg_bounds); its source is the row's key at the same distance from the
+// key's start.  A word takes one unaligned 8-byte read of the key blob per row it overlaps
+// (rows average a few words, so mostly one or two).  Bytes past blob_bytes in the last word
+// are zeros.
+__global__ __launch_bounds__(kAT) void k_agg_bytes(const uint8_t* __restrict__ blob, uint64_t key_end8,
+                                                   const uint64_t* __restrict__ offsets,
+                                                   const uint64_t* __restrict__ rowsrc,
+                                                   const uint64_t* __restrict__ bounds, uint64_t n,
+                                                   uint64_t blob_bytes, uint8_t* __restrict__ out) {
+  const uint64_t wbase = (uint64_t)blockIdx.x * kAT;
+  const uint64_t nw = (blob_bytes + 7) / 8;
+  if (wbase >= nw) return;
+  const uint64_t wend = min(nw, wbase + kAT);
+  // offsets has n + 1 entries, offsets[0] = 0, offsets[n] = blob_bytes
+  const uint64_t r_lo = bounds[blockIdx.x];
+  const uint64_t r_hi = blockIdx.x + 1 < gridDim.x ? bounds[blockIdx.x + 1] : n - 1;
+  const uint64_t wi = wbase + threadIdx.x;
+  if (wi >= wend) return;
+  const uint64_t a = 8 * wi, aend = min(a + 8, blob_bytes);
+  uint64_t r = first_above(offsets, r_lo + 1, r_hi + 1, a) - 1;
+  uint64_t o0 = offsets[r], o1 = offsets[r + 1];
+  uint64_t v = 0;
+  for (uint64_t p = a; p < aend;) {
+    while (o1 <= p) {  // offsets[n] = blob_bytes > p ends it
+      ++r;
+      o0 = o1;
+      o1 = offsets[r + 1];
+    }
+    const uint64_t cnt = min(o1, aend) - p;  // bytes of row r in this word, 1..8
+    // the read may run past the row's key, never past the blob's readable end
+    const uint64_t x = load8(blob, rowsrc[r] + (p - o0), key_end8);
+    v |= (cnt >= 8 ? x : x & ((1ull << (8 * cnt)) - 1)) << (8 * (p - a));
+    p += cnt;
+  }
+  if (((uintptr_t)out & 7) == 0) {
+    *reinterpret_cast<uint64_t*>(out + a) = v;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[a + j] = (uint8_t)(v >> (8 * j));
+  }
+}
+
+}  // namespace
+
+// Scratch of the aggregation and the last plan, kept in the context and grown as needed.
+struct AggScratch {
+  uint32_t* c = nullptr;
+  uint64_t *rowbase = nullptr, *keybytes = nullptr, *Z = nullptr;
+  uint32_t *bmin = nullptr, *smin = nullptr;
+  AggTop* top = nullptr;
+  uint64_t cap = 0;  // keys
+  uint64_t* rowsrc = nullptr;
+  uint64_t rows_cap = 0;
+  uint64_t* bounds = nullptr;  // the emit chunks' first owners (k_agg_bounds)
+  uint64_t bounds_cap = 0;
+  void* tmp = nullptr;
+  size_t tmp_cap = 0;
+  // the last plan
+  bool have_plan = false, sized = false;
+  const uint8_t* keys = nullptr;
+  const uint64_t* koff = nullptr;
+  uint64_t m = 0, n = 0, blob_bytes = 0, key_end8 = 0;
+  uint32_t depth_cap = 0;
+  void release() {
+    dfree(c);
+    dfree(rowbase);
+    dfree(keybytes);
+    dfree(Z);
+    dfree(bmin);
+    dfree(smin);
+    dfree(top);
+    dfree(rowsrc);
+    dfree(bounds);
+    dfree(tmp);
+    cap = rows_cap = bounds_cap = 0;
+    tmp_cap = 0;
+    have_plan = false;
+  }
+};
+
+void agg_scratch_free(s3imph_ctx* c) {
+  if (c->agg) {
+    c->agg->release();
+    delete c->agg;
+    c->agg = nullptr;
+  }
+}
+
+namespace {
+
+void scan_u64(AggScratch& a, uint64_t* v, uint64_t count, uint64_t init, hipStream_t s) {
+  size_t need = 0;
+  HIPCHECK(rocprim::exclusive_scan(nullptr, need, v, v, init, count, rocprim::plus<uint64_t>(), s));
+  if (need > a.tmp_cap) {
+    dfree(a.tmp);
+    a.tmp_cap = 0;
+    HIPCHECK(hipMalloc(&a.tmp, need));
+    a.tmp_cap = need;
+  }
+  HIPCHECK(rocprim::exclusive_scan(a.tmp, need, v, v, init, count, rocprim::plus<uint64_t>(), s));
+}
+
+}  // namespace
+
+// Plan: the key pass and the scans for m keys in HBM; fills *info, keeps the plan in the
+// context.  Waits for the stream.
+int aggregate_plan(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes, uint64_t m,
+                   uint32_t max_depth, s3imph_agg_info* info, hipStream_t s, std::string* msg) {
+  std::memset(info, 0, sizeof *info);
+  info->first_unsorted = UINT64_MAX;
+  info->n_objects = m;
+  if (!c->agg) c->agg = new AggScratch();
+  AggScratch& a = *c->agg;
+  a.have_plan = false;
+  if (m == 0) {
+    a.keys = nullptr;
+    a.koff = nullptr;
+    a.m = a.n = a.blob_bytes = 0;
+    a.have_plan = true;
+    return S3IMPH_OK;
+  }
+  const uint64_t nb = (m + kAB - 1) / kAB, nsb = (nb + kAS - 1) / kAS;
+  if (m > a.cap) {
+    a.release();
+    dalloc(a.c, m);
+    dalloc(a.rowbase, m + 1);
+    dalloc(a.keybytes, m + 1);
+    dalloc(a.Z, m + 1);
+    dalloc(a.bmin, nb);
+    dalloc(a.smin, nsb);
+    dalloc(a.top, 1);
+    a.cap = m;
+  }
+  const uint32_t cap = max_depth ? max_depth : 0xffffffffu;
+  const AggTop top0{~0ull, ~0ull, 0, 0};
+  AggTop top = top0;
+  HIPCHECK(hipMemcpyAsync(a.top, &top0, sizeof top0, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemsetAsync(a.rowbase + m, 0, 8, s));
+  HIPCHECK(hipMemsetAsync(a.keybytes + m, 0, 8, s));
+  k_agg_keys<<<(unsigned)nb, kAB, 0, s>>>(keys, koff, m, cap, a.c, a.rowbase, a.keybytes, a.bmin, a.top);
+  k_agg_super<<<(unsigned)nsb, kAS, 0, s>>>(a.bmin, nb, a.smin);
+  HIPCHECK(hipGetLastError());
+  scan_u64(a, a.rowbase, m + 1, 1, s);  // + 1: the root row
+  scan_u64(a, a.keybytes, m + 1, 0, s);
+  a.sized = sizes != nullptr;
+  uint64_t tot[4] = {0, 0, 0, 0};  // rows, row bytes, size sum, end of the key blob
+  if (sizes) {
+    HIPCHECK(hipMemcpyAsync(a.Z, sizes, m * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHECK(hipMemsetAsync(a.Z + m, 0, 8, s));
+    scan_u64(a, a.Z, m + 1, 0, s);
+    HIPCHECK(hipMemcpyAsync(&tot[2], a.Z + m, 8, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHECK(hipMemcpyAsync(&top, a.top, sizeof top, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(&tot[3], koff + m, 8, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(&tot[0], a.rowbase + m, 8, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(&tot[1], a.keybytes + m, 8, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  info->n_prefixes = tot[0];
+  info->blob_bytes = tot[1];
+  info->total_bytes = tot[2];
+  info->max_depth_seen = top.maxd;
+  info->first_unsorted = top.first_unsorted;
+  if (top.first_unsorted != ~0ull) {
+    *msg = "aggregate: object keys are not byte-sorted: key " + std::to_string(top.first_unsorted) +
+           " is smaller than key " + std::to_string(top.first_unsorted - 1);
+    return S3IMPH_ERR_INVALID;
+  }
+  if (top.first_deep != ~0ull) {
+    *msg = "aggregate: key " + std::to_string(top.first_deep) + " has more than 65535 '/' (the depth is a uint16)";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (tot[0] > kMaxRows) {
+    *msg = "aggregate: more than 2^30 prefixes on one GPU (the MPHF's level 0 past 2^31 positions): "
+           "shard them over several GPUs";
+    return S3IMPH_ERR_INVALID;
+  }
+  a.keys = keys;
+  a.koff = koff;
+  a.m = m;
+  a.n = tot[0];
+  a.blob_bytes = tot[1];
+  a.key_end8 = (tot[3] + 7) & ~7ull;
+  a.depth_cap = cap;
+  a.have_plan = true;
+  return S3IMPH_OK;
+}
+
+// Fill: the rows of the last plan.  Waits for the stream.
+int aggregate_fill(s3imph_ctx* c, uint8_t* blob, uint64_t blob_cap, uint64_t* offsets, uint32_t* depth,
+                   uint64_t* ocnt, uint64_t* tbytes, uint64_t n_cap, hipStream_t s, std::string* msg) {
+  if (!c->agg || !c->agg->have_plan) {
+    *msg = "aggregate: fill without a plan";
+    return S3IMPH_ERR_STATE;
+  }
+  AggScratch& a = *c->agg;
+  if (n_cap < a.n || blob_cap < ((a.blob_bytes + 7) & ~7ull)) {
+    *msg = "aggregate: the plan needs " + std::to_string(a.n) + " rows and " +
+           std::to_string((a.blob_bytes + 7) & ~7ull) + " blob bytes";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (!offsets || (a.n && (!depth || !ocnt || !tbytes)) || (a.blob_bytes && !blob)) {
+    *msg = "aggregate: null output array";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (a.n == 0) {
+    HIPCHECK(hipMemsetAsync(offsets, 0, 8, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return S3IMPH_OK;
+  }
+  if (a.n > a.rows_cap) {
+    a.rows_cap = 0;
+    dalloc(a.rowsrc, a.n);
+    a.rows_cap = a.n;
+  }
+  const uint64_t nb = (a.m + kAB - 1) / kAB, nsb = (nb + kAS - 1) / kAS;
+  const uint64_t nw = (a.blob_bytes + 7) / 8;
+  const uint64_t rchunks = (a.n + kAT - 1) / kAT, wchunks = (nw + kAT - 1) / kAT;
+  if (std::max(rchunks, wchunks) > a.bounds_cap) {
+    a.bounds_cap = 0;
+    dalloc(a.bounds, std::max(rchunks, wchunks));
+    a.bounds_cap = std::max(rchunks, wchunks);
+  }
+  k_agg_bounds<<<(unsigned)((rchunks + kAT - 1) / kAT), kAT, 0, s>>>(a.rowbase, a.m + 1, kAT, 1, rchunks, a.bounds);
+  k_agg_rows<<<(unsigned)rchunks, kAT, 0, s>>>(a.keys, a.koff, a.m, a.depth_cap, a.c, a.rowbase, a.keybytes, a.bounds,
+                                               a.sized ? a.Z : nullptr, a.bmin, a.smin, nb, nsb, a.n, a.blob_bytes,
+                                               offsets, depth, ocnt, tbytes, a.rowsrc);
+  if (nw) {
+    k_agg_bounds<<<(unsigned)((wchunks + kAT - 1) / kAT), kAT, 0, s>>>(offsets, a.n + 1, 8ull * kAT, 0, wchunks,
+                                                                      a.bounds);
+    k_agg_bytes<<<(unsigned)wchunks, kAT, 0, s>>>(a.keys, a.key_end8, offsets, a.rowsrc, a.bounds, a.n, a.blob_bytes,
+                                                  blob);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(s));
+  return S3IMPH_OK;
+}
+
+namespace {
+
+struct DevGuard {
+  std::vector<void*> p;
+  template <typename T>
+  void make(T*& q, uint64_t count) {
+    dalloc(q, count);
+    p.push_back(q);
+  }
+  void drop(void* q) {
+    if (!q) return;
+    for (void*& x : p)
+      if (x == q) {
+        (void)hipFree(x);
+        x = nullptr;
+      }
+  }
+  ~DevGuard() {
+    for (void* q : p)
+      if (q) (void)hipFree(q);
+  }
+};
+
+// The prefix rows of a host listing, left in HBM (owned by g).
+struct DevRows {
+  uint64_t n = 0, blob_bytes = 0;
+  uint8_t* blob = nullptr;
+  uint64_t *offsets = nullptr, *ocnt = nullptr, *tbytes = nullptr;
+  uint32_t* depth = nullptr;
+};
+
+// H2D of the listing, plan, fill; the listing's device copy is freed before returning.
+int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes,
+                   uint64_t m, uint32_t max_depth, DevRows* out, std::string* msg) {
+  hipStream_t s = c->own_stream;
+  uint8_t* d_keys = nullptr;
+  uint64_t *d_koff = nullptr, *d_sizes = nullptr;
+  if (m) {
+    const uint64_t b0 = koff[0], nbytes = koff[m] - b0;
+    g.make(d_keys, ((nbytes + 7) & ~7ull) + 16);
+    g.make(d_koff, m + 1);
+    if (nbytes) HIPCHECK(hipMemcpy(d_keys, keys + b0, nbytes, hipMemcpyHostToDevice));
+    staged_copy(c, true, d_koff, koff, (m + 1) * 8, b0);
+    if (sizes) {
+      g.make(d_sizes, m);
+      staged_copy(c, true, d_sizes, sizes, m * 8);
+    }
+  }
+  s3imph_agg_info info;
+  int rc = aggregate_plan(c, d_keys, d_koff, d_sizes, m, max_depth, &info, s, msg);
+  if (rc != S3IMPH_OK) return rc;
+  out->n = info.n_prefixes;
+  out->blob_bytes = info.blob_bytes;
+  g.make(out->blob, ((info.blob_bytes + 7) & ~7ull) + 16);
+  g.make(out->offsets, out->n + 1);
+  g.make(out->depth, out->n);
+  g.make(out->ocnt, out->n);
+  g.make(out->tbytes, out->n);
+  rc = aggregate_fill(c, out->blob, (info.blob_bytes + 7) & ~7ull, out->offsets, out->depth, out->ocnt, out->tbytes,
+                      out->n, s, msg);
+  c->agg->have_plan = false;  // the listing's copy goes away with this call
+  g.drop(d_keys);
+  g.drop(d_koff);
+  g.drop(d_sizes);
+  return rc;
+}
+
+template <typename T>
+T* host_array(uint64_t count) {
+  T* p = static_cast<T*>(std::malloc(std::max<uint64_t>(count, 1) * sizeof(T)));
+  if (!p) throw std::bad_alloc();
+  return p;
+}
+
+// A host listing's pointers: the offsets whenever there are keys, the blob whenever the keys
+// have bytes (a listing of empty keys may come with a NULL blob).
+bool listing_given(const uint8_t* keys, const uint64_t* koff, uint64_t m) {
+  return m == 0 || (koff && (keys || koff[m] == koff[0]));
+}
+
+bool is_dir(const std::string& p) {
+  struct stat st;
+  return ::stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
+}
+
+}  // namespace
+
+}  // namespace s3imph
+
+using namespace s3imph;
+
+extern "C" {
+
+int s3imph_aggregate_plan_device(s3imph_ctx* c, const uint8_t* d_keys, const uint64_t* d_key_offsets,
+                                 const uint64_t* d_sizes, uint64_t m, uint32_t max_depth, s3imph_agg_info* info,
+                                 void* stream) {
+  if (!c || !info || (m && (!d_keys || !d_key_offsets))) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  std::string msg;
+  try {
+    HIPCHECK(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
+    const int rc = retry_on_nomem(c, s, &msg, [&] {
+      return aggregate_plan(c, d_keys, d_key_offsets, d_sizes, m, max_depth, info, s, &msg);
+    });
+    c->last_msg = msg;
+    return rc;
+  } catch (const Fail& f) {
+    c->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+int s3imph_aggregate_fill_device(s3imph_ctx* c, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offsets,
+                                 uint32_t* d_depth, uint64_t* d_object_count, uint64_t* d_total_bytes,
+                                 uint64_t n_cap, void* stream) {
+  if (!c) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  std::string msg;
+  try {
+    HIPCHECK(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
+    const int rc = aggregate_fill(c, d_blob, blob_cap, d_offsets, d_depth, d_object_count, d_total_bytes, n_cap, s,
+                                  &msg);
+    c->last_msg = msg;
+    return rc;
+  } catch (const Fail& f) {
+    c->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+int s3imph_aggregate_host(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
+                          uint64_t m, uint32_t max_depth, uint8_t** blob, uint64_t** offsets, uint32_t** depth,
+                          uint64_t** object_count, uint64_t** total_bytes, uint64_t* n, char* err, size_t errlen) {
+  if (!blob || !offsets || !depth || !object_count || !total_bytes || !n || !listing_given(keys, key_offsets, m))
+    return S3IMPH_ERR_INVALID;
+  *blob = nullptr;
+  *offsets = nullptr;
+  *depth = nullptr;
+  *object_count = *total_bytes = nullptr;
+  *n = 0;
+  std::string msg;
+  auto drop = [&] {
+    std::free(*blob);
+    std::free(*offsets);
+    std::free(*depth);
+    std::free(*object_count);
+    std::free(*total_bytes);
+    *blob = nullptr;
+    *offsets = nullptr;
+    *depth = nullptr;
+    *object_count = *total_bytes = nullptr;
+  };
+  try {
+    if (m == 0) {  // Drain returns nil
+      *offsets = host_array<uint64_t>(1);
+      (*offsets)[0] = 0;
+      return S3IMPH_OK;
+    }
+    s3imph_ctx* c = default_ctx(device, &msg);
+    if (!c) {
+      set_err(err, errlen, "aggregate: " + msg);
+      return S3IMPH_ERR_HIP;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHECK(hipSetDevice(c->device));
+    const int rc = retry_on_nomem(c, c->own_stream, &msg, [&] {
+      DevGuard g;
+      DevRows r;
+      const int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg);
+      if (rc2 != S3IMPH_OK) return rc2;
+      drop();
+      *blob = host_array<uint8_t>(r.blob_bytes);
+      *offsets = host_array<uint64_t>(r.n + 1);
+      *depth = host_array<uint32_t>(r.n);
+      *object_count = host_array<uint64_t>(r.n);
+      *total_bytes = host_array<uint64_t>(r.n);
+      if (r.blob_bytes) HIPCHECK(hipMemcpy(*blob, r.blob, r.blob_bytes, hipMemcpyDeviceToHost));
+      staged_copy(c, false, *offsets, r.offsets, (r.n + 1) * 8);
+      staged_copy(c, false, *depth, r.depth, r.n * 4);
+      staged_copy(c, false, *object_count, r.ocnt, r.n * 8);
+      staged_copy(c, false, *total_bytes, r.tbytes, r.n * 8);
+      *n = r.n;
+      return (int)S3IMPH_OK;
+    });
+    if (rc != S3IMPH_OK) {
+      drop();
+      *n = 0;
+      set_err(err, errlen, msg);
+    }
+    return rc;
+  } catch (const Fail& f) {
+    drop();
+    *n = 0;
+    set_err(err, errlen, "aggregate: " + f.msg);
+    return f.code;
+  } catch (const std::bad_alloc&) {
+    drop();
+    *n = 0;
+    set_err(err, errlen, "aggregate: out of host memory");
+    return S3IMPH_ERR_NOMEM;
+  }
+}
+
+int s3imph_index_from_objects_host(int device, const uint8_t* keys, const uint64_t* key_offsets,
+                                   const uint64_t* sizes, uint64_t m, uint32_t max_depth, const char* out_dir,
+                                   char* err, size_t errlen) {
+  if (!out_dir || !listing_given(keys, key_offsets, m)) return S3IMPH_ERR_INVALID;
+  const std::string dir = out_dir;
+  if (!is_dir(dir)) {
+    set_err(err, errlen, "create mph file: open " + dir + "/mph.bin: no such directory");
+    return S3IMPH_ERR_IO;
+  }
+  std::string msg;
+  try {
+    uint64_t n = 0;
+    uint32_t md = 0;
+    std::vector<uint8_t> mph, blob;
+    std::vector<uint64_t> fp, pos, offs, send, dpos, doff, ocnt, tbytes;
+    std::vector<uint32_t> depth, maxds;
+    if (m) {
+      s3imph_ctx* c = default_ctx(device, &msg);
+      if (!c) {
+        set_err(err, errlen, "aggregate: " + msg);
+        return S3IMPH_ERR_HIP;
+      }
+      std::lock_guard<std::mutex> lk(c->mu);
+      HIPCHECK(hipSetDevice(c->device));
+      hipStream_t s = c->own_stream;
+      // one device residency: the rows stay in HBM from the aggregation to the last array
+      const int rc = retry_on_nomem(c, s, &msg, [&]() -> int {
+        DevGuard g;
+        DevRows r;
+        int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg);
+        if (rc2 != S3IMPH_OK) return rc2;
+        n = r.n;
+        uint64_t *d_fp = nullptr, *d_pos = nullptr, *d_send = nullptr, *d_dpos = nullptr, *d_doff = nullptr;
+        uint32_t *d_depth = nullptr, *d_maxds = nullptr;
+        g.make(d_fp, n);
+        g.make(d_pos, n);
+        s3imph_build_info binfo;
+        rc2 = build_single(c, r.blob, r.offsets, nullptr, n, d_fp, d_pos, s, &binfo, &msg);
+        if (rc2 != S3IMPH_OK) return rc2;
+        HIPCHECK(hipStreamSynchronize(s));
+        g.make(d_send, n);
+        g.make(d_dpos, n);
+        g.make(d_depth, n);
+        g.make(d_maxds, n);
+        uint64_t cap = 64;
+        for (int attempt = 0; attempt < 2; ++attempt) {
+          g.make(d_doff, cap);
+          rc2 = finalize_device(c, r.blob, r.offsets, r.depth, n, d_depth, d_send, d_maxds, d_dpos, d_doff, cap, &md,
+                                s, &msg);
+          if (rc2 == S3IMPH_OK) break;
+          if (rc2 != S3IMPH_ERR_INVALID || attempt) return rc2;
+          cap = (uint64_t)md + 2;
+          g.drop(d_doff);
+          d_doff = nullptr;
+        }
+        HIPCHECK(hipStreamSynchronize(s));
+        uint64_t mlen = 0;
+        mph.resize(binfo.mph_bin_len);
+        rc2 = marshal_locked(c, mph.data(), mph.size(), &mlen, &msg);
+        if (rc2 != S3IMPH_OK) return rc2;
+        mph.resize(mlen);
+        blob.resize(r.blob_bytes);
+        offs.resize(n + 1);
+        doff.resize((uint64_t)md + 2);
+        for (auto* v : {&fp, &pos, &send, &dpos, &ocnt, &tbytes}) v->resize(n);
+        depth.resize(n);
+        maxds.resize(n);
+        if (r.blob_bytes) HIPCHECK(hipMemcpy(blob.data(), r.blob, r.blob_bytes, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(doff.data(), d_doff, doff.size() * 8, hipMemcpyDeviceToHost));
+        staged_copy(c, false, offs.data(), r.offsets, (n + 1) * 8);
+        staged_copy(c, false, fp.data(), d_fp, n * 8);
+        staged_copy(c, false, pos.data(), d_pos, n * 8);
+        staged_copy(c, false, send.data(), d_send, n * 8);
+        staged_copy(c, false, dpos.data(), d_dpos, n * 8);
+        staged_copy(c, false, ocnt.data(), r.ocnt, n * 8);
+        staged_copy(c, false, tbytes.data(), r.tbytes, n * 8);
+        staged_copy(c, false, depth.data(), d_depth, n * 4);
+        staged_copy(c, false, maxds.data(), d_maxds, n * 4);
+        return S3IMPH_OK;
+      });
+      if (rc != S3IMPH_OK) {
+        set_err(err, errlen, msg);
+        return rc;
+      }
+    } else {
+      offs = {0};
+      doff = {0, 0};  // writeEmpty-like: maxDepth 0 -> offsets [0, 0]
+    }
+    int rc = write_index_files(dir, mph.data(), mph.size(), fp.data(), pos.data(), n, blob.data(), offs.data(), &msg);
+    if (rc == S3IMPH_OK)
+      rc = write_finalize_files(dir, depth.data(), send.data(), maxds.data(), doff.data(), doff.size(), dpos.data(), n,
+                                &msg);
+    if (rc == S3IMPH_OK) rc = write_stats_files(dir, ocnt.data(), tbytes.data(), n, &msg);
+    if (rc == S3IMPH_OK) rc = write_manifest(dir, n, md, &msg);
+    if (rc != S3IMPH_OK) set_err(err, errlen, msg);
+    return rc;
+  } catch (const Fail& f) {
+    set_err(err, errlen, "aggregate: " + f.msg);
+    return f.code;
+  } catch (const std::bad_alloc&) {
+    set_err(err, errlen, "aggregate: out of host memory");
+    return S3IMPH_ERR_NOMEM;
+  }
+}
+
+}  // extern "C"

@@ -2501,18 +2501,20 @@ bool reclaim_cached(s3imph_ctx* keep, const void* keep_set) {
       if (!c || c == keep) continue;
       std::unique_lock<std::mutex> lk(c->mu, std::try_to_lock);
       if (!lk.owns_lock()) continue;  // building right now
-      if (!c->hist && !c->s_blob && !c->fin) continue;  // nothing cached
+      if (!c->hist && !c->s_blob && !c->fin && !c->agg) continue;  // nothing cached
       (void)hipSetDevice(c->device);
       if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
       free_workspace(c);
       fin_scratch_free(c);
+      agg_scratch_free(c);
       c->have_build = false;
       c->rank_valid = false;
       any = true;
     }
   }
-  if (keep && keep->fin) {
+  if (keep && (keep->fin || keep->agg)) {
     fin_scratch_free(keep);
+    agg_scratch_free(keep);
     any = true;
   }
   if (keep) (void)hipSetDevice(keep->device);
@@ -3093,6 +3095,7 @@ int s3imph_ctx_destroy(s3imph_ctx* c) {
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   free_workspace(c);
   fin_scratch_free(c);
+  agg_scratch_free(c);
   if (c->d.xo) (void)hipStreamSynchronize(c->d.xo);
   delete c->d.xcomm;
   c->d.xcomm = nullptr;
@@ -3502,6 +3505,7 @@ int s3imph_release_workspaces(void) {
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     free_workspace(c);
     fin_scratch_free(c);
+    agg_scratch_free(c);
     c->have_build = false;
     c->rank_valid = false;
   }

@@ -200,11 +200,13 @@ using s3imph::Stager;
 
 namespace s3imph {
 struct FinScratch;  // s3imph_finalize.hip
+struct AggScratch;  // s3imph_aggregate.hip
 }
 
 struct s3imph_ctx {
   int device = 0;
   s3imph::FinScratch* fin = nullptr;  // finalize-pass scratch (s3imph_finalize.hip), lazily made
+  s3imph::AggScratch* agg = nullptr;  // aggregation scratch and the last plan (s3imph_aggregate.hip), lazily made
   uint32_t* mid = nullptr;            // k_mid_levels scratch (kMidScratchU32, or the 256-workgroup form's), lazily made
   uint64_t mid_cap = 0;               // ... its u32 words
   Rec* split = nullptr;               // k_tile_split scratch, made for sets big enough for 2^15+ tiles
@@ -355,6 +357,13 @@ int finalize_device(s3imph_ctx* c, const uint8_t* blob, const uint64_t* offsets,
 int finalize_from_host(int device, const uint8_t* blob, const uint64_t* offsets, const uint32_t* depths, uint64_t n,
                        const std::string& dir, std::string* msg);
 void fin_scratch_free(s3imph_ctx* c);
+// Prefix aggregation (s3imph_aggregate.hip): plan (key pass + scans, fills *info) and fill (the
+// rows of the last plan) over an object listing in HBM; both wait for the stream.
+int aggregate_plan(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes, uint64_t m,
+                   uint32_t max_depth, s3imph_agg_info* info, hipStream_t s, std::string* msg);
+int aggregate_fill(s3imph_ctx* c, uint8_t* blob, uint64_t blob_cap, uint64_t* offsets, uint32_t* depth,
+                   uint64_t* ocnt, uint64_t* tbytes, uint64_t n_cap, hipStream_t s, std::string* msg);
+void agg_scratch_free(s3imph_ctx* c);
 // A context (s3imph_ctx_create) whose multi-GPU collectives go through `comm` (owned).
 s3imph_ctx* make_dist_ctx(int device, Comm* comm, int rank, int nranks, std::string* msg);
 

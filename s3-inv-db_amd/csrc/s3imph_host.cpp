@@ -292,6 +292,22 @@ int write_finalize_files(const std::string& dir, const uint32_t* depth, const ui
   return S3IMPH_OK;
 }
 
+// object_count.u64 / total_bytes.u64: the ArrayWriters IndexBuilder.Add feeds one value per
+// row (indexbuild.go:179-184), with its messages.
+int write_stats_files(const std::string& dir, const uint64_t* object_count, const uint64_t* total_bytes, uint64_t n,
+                      std::string* msg) {
+  std::string m;
+  if (!write_u64_array(dir + "/object_count.u64", object_count, n, 0, &m)) {
+    *msg = "write object_count: " + m;
+    return S3IMPH_ERR_IO;
+  }
+  if (!write_u64_array(dir + "/total_bytes.u64", total_bytes, n, 0, &m)) {
+    *msg = "write total_bytes: " + m;
+    return S3IMPH_ERR_IO;
+  }
+  return S3IMPH_OK;
+}
+
 int write_index_files(const std::string& dir, const uint8_t* mph_bin, uint64_t mph_len, const uint64_t* fp,
                       const uint64_t* pos, uint64_t n, const uint8_t* blob, const uint64_t* offsets,
                       std::string* msg) {

@@ -11,8 +11,10 @@ Mirrors the reference's MPHF stage interface, ``format.StreamingMPHFBuilder``
     b.close()                                # Close (:105)
 
 plus the device-resident API that bench.py times (``DeviceBuilder``), the
-multi-GPU rank API (``DistBuilder``), the batched lookup (``MPHF``) and the reader,
-``Index`` (indexread.Index: Open / Lookup / Stats / Descendants* over a batch).
+multi-GPU rank API (``DistBuilder``), the batched lookup (``MPHF``), the reader,
+``Index`` (indexread.Index: Open / Lookup / Stats / Descendants* over a batch), and the front
+of the pipeline: ``aggregate`` (extsort.Aggregator + SortPrefixRows: object listing -> prefix
+rows) and ``build_index_from_objects`` (object listing -> index directory).
 
 Every compute call goes through the HIP library; there is no CPU fallback.
 If libs3imph.so is missing, importing this module raises.
@@ -71,6 +73,8 @@ EXPORTS = (
     "s3imph_index_open", "s3imph_index_attach", "s3imph_index_close", "s3imph_index_count",
     "s3imph_index_max_depth", "s3imph_index_last_error", "s3imph_index_lookup_device",
     "s3imph_index_nodes_device", "s3imph_index_descendants_plan", "s3imph_index_descendants_fill",
+    "s3imph_aggregate_plan_device", "s3imph_aggregate_fill_device", "s3imph_aggregate_host",
+    "s3imph_index_from_objects_host",
 )
 
 
@@ -117,6 +121,18 @@ class IndexArrays(ctypes.Structure):
         ("d_depth_positions", ctypes.c_void_p), ("max_depth", ctypes.c_uint32),
         ("d_object_count", ctypes.c_void_p), ("d_total_bytes", ctypes.c_void_p),
     ]
+
+
+class AggInfo(ctypes.Structure):
+    """s3imph_agg_info: what an aggregation plan found (include/s3imph.h, section 5d)."""
+    _fields_ = [
+        ("n_prefixes", ctypes.c_uint64), ("blob_bytes", ctypes.c_uint64), ("n_objects", ctypes.c_uint64),
+        ("total_bytes", ctypes.c_uint64), ("first_unsorted", ctypes.c_uint64),
+        ("max_depth_seen", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
 
 # s3imph_node: what Index.nodes returns, one record per queried position
@@ -187,6 +203,11 @@ def _load():
         "s3imph_index_descendants_plan": (i32, [vp, vp, vp, u64, i32, ctypes.c_int32, u64, u64, vp, vp, u64,
                                                 P(u64), P(u64), vp]),
         "s3imph_index_descendants_fill": (i32, [vp, vp, u64, vp]),
+        "s3imph_aggregate_plan_device": (i32, [vp, vp, vp, vp, u64, ctypes.c_uint32, P(AggInfo), vp]),
+        "s3imph_aggregate_fill_device": (i32, [vp, vp, u64, vp, vp, vp, vp, u64, vp]),
+        "s3imph_aggregate_host": (i32, [i32, vp, vp, vp, u64, ctypes.c_uint32, P(vp), P(vp), P(vp), P(vp), P(vp),
+                                        P(u64), cp, sz]),
+        "s3imph_index_from_objects_host": (i32, [i32, vp, vp, vp, u64, ctypes.c_uint32, cp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -483,6 +504,45 @@ class DeviceBuilder:
         return {"depth": depth[:n], "subtree_end": send[:n], "max_depth_in_subtree": mds[:n],
                 "depth_positions": dpos[:n], "depth_offsets": doff[: md.value + 2], "max_depth": md.value}
 
+    def aggregate_plan(self, d_keys, d_key_offsets, m: int, d_sizes=None, max_depth: int = 0, stream=None) -> dict:
+        """s3imph_aggregate_plan_device: size the prefix rows of a byte-sorted object listing in
+        HBM (AddObject over every key, aggregator.go:44-61).  Returns s3imph_agg_info as a dict
+        (n_prefixes, blob_bytes, n_objects, total_bytes, first_unsorted, max_depth_seen); a
+        refusal raises MPHFError with that dict as ``.info``.  The key tensors must stay valid
+        and unchanged until aggregate_fill."""
+        info = AggInfo()
+        rc = LIB.s3imph_aggregate_plan_device(self._h, _dev_ptr(d_keys), _dev_ptr(d_key_offsets), _dev_ptr(d_sizes),
+                                              m, max_depth, ctypes.byref(info), _stream_ptr(stream))
+        self.last_agg = info.as_dict()
+        if rc != OK:
+            e = MPHFError(rc, self.last_error() or f"aggregate: {status_string(rc)}")
+            e.info = self.last_agg
+            raise e
+        return self.last_agg
+
+    def aggregate_fill(self, n_cap: int | None = None, blob_cap: int | None = None, device=None, stream=None) -> dict:
+        """s3imph_aggregate_fill_device: the rows of the last plan (Drain + SortPrefixRows) as
+        torch tensors: blob (uint8, padded with zeros to 8 bytes), offsets (int64, n + 1), depth
+        (int32), object_count / total_bytes (int64 holding the u64 bits), n, blob_bytes.  The
+        capacities default to what the plan asked for."""
+        import torch
+        info = getattr(self, "last_agg", None) or {"n_prefixes": 0, "blob_bytes": 0}
+        n, nbytes = info["n_prefixes"], info["blob_bytes"]
+        n_cap = n if n_cap is None else n_cap
+        blob_cap = (nbytes + 7) // 8 * 8 if blob_cap is None else blob_cap
+        dev = f"cuda:{self.device}" if device is None else device
+        blob = torch.empty(max(blob_cap, 8), dtype=torch.uint8, device=dev)
+        offs = torch.empty(max(n_cap, n) + 1, dtype=torch.int64, device=dev)
+        depth = torch.empty(max(n_cap, 1), dtype=torch.int32, device=dev)
+        ocnt = torch.empty(max(n_cap, 1), dtype=torch.int64, device=dev)
+        tbytes = torch.empty(max(n_cap, 1), dtype=torch.int64, device=dev)
+        rc = LIB.s3imph_aggregate_fill_device(self._h, _dev_ptr(blob), blob_cap, _dev_ptr(offs), _dev_ptr(depth),
+                                              _dev_ptr(ocnt), _dev_ptr(tbytes), n_cap, _stream_ptr(stream))
+        if rc != OK:
+            raise MPHFError(rc, self.last_error() or f"aggregate: {status_string(rc)}")
+        return {"blob": blob[: (nbytes + 7) // 8 * 8], "offsets": offs[: n + 1], "depth": depth[:n],
+                "object_count": ocnt[:n], "total_bytes": tbytes[:n], "n": n, "blob_bytes": nbytes}
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             LIB.s3imph_ctx_destroy(self._h)
@@ -506,6 +566,58 @@ def finalize_index_host(blob: np.ndarray, offsets: np.ndarray, out_dir: str, dep
     rc = LIB.s3imph_finalize_index_host(device, _np_ptr(blob), _np_ptr(offsets), _np_ptr(dp) if dp is not None else None,
                                         len(offsets) - 1, out_dir.encode(), err, 1024)
     _check(rc, err)
+
+
+def _listing(keys_blob, key_offsets, sizes):
+    blob = np.ascontiguousarray(keys_blob, np.uint8)
+    offs = np.ascontiguousarray(key_offsets, np.uint64)
+    m = len(offs) - 1
+    sz = None if sizes is None else np.ascontiguousarray(sizes, np.uint64)
+    if sz is not None and len(sz) != m:
+        raise ValueError("sizes must hold one entry per key")
+    return blob, offs, sz, m
+
+
+def aggregate(keys_blob: np.ndarray, key_offsets: np.ndarray, sizes: np.ndarray | None, max_depth: int = 0,
+              device: int = 0):
+    """extsort.Aggregator + SortPrefixRows (aggregator.go:44-76, :138-) on the GPU
+    (s3imph_aggregate_host): the byte-sorted object listing (keys in the blob / offsets layout,
+    one size per key; max_depth 0 = unlimited) -> (prefix_blob u8, prefix_offsets u64[n + 1],
+    depth u32[n], object_count u64[n], total_bytes u64[n]) in the reference's row order."""
+    blob, offs, sz, m = _listing(keys_blob, key_offsets, sizes)
+    out = [ctypes.c_void_p() for _ in range(5)]
+    n = ctypes.c_uint64()
+    err = ctypes.create_string_buffer(1024)
+    rc = LIB.s3imph_aggregate_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), m, max_depth,
+                                   *[ctypes.byref(p) for p in out], ctypes.byref(n), err, 1024)
+    try:
+        _check(rc, err)
+        nn = n.value
+
+        def take(p, dtype, count):
+            a = np.zeros(count, dtype)
+            if count and p.value:
+                ctypes.memmove(a.ctypes.data, p.value, a.nbytes)
+            return a
+
+        offsets = take(out[1], np.uint64, nn + 1)
+        return (take(out[0], np.uint8, int(offsets[-1])), offsets, take(out[2], np.uint32, nn),
+                take(out[3], np.uint64, nn), take(out[4], np.uint64, nn))
+    finally:
+        for p in out:
+            if p.value:
+                LIB.s3imph_free(p)
+
+
+def build_index_from_objects(keys_blob: np.ndarray, key_offsets: np.ndarray, sizes: np.ndarray | None, out_dir: str,
+                             max_depth: int = 0, device: int = 0) -> None:
+    """Object listing in, index directory out (s3imph_index_from_objects_host): aggregation,
+    MPHF build and finalize in one device residency; writes the MPHF-stage files, the finalize
+    files, object_count.u64 / total_bytes.u64 and manifest.json into out_dir."""
+    blob, offs, sz, m = _listing(keys_blob, key_offsets, sizes)
+    err = ctypes.create_string_buffer(1024)
+    _check(LIB.s3imph_index_from_objects_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), m, max_depth,
+                                              os.fsencode(out_dir), err, 1024), err)
 
 
 def write_manifest(out_dir: str, node_count: int, max_depth: int) -> None:
