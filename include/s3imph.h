@@ -349,7 +349,10 @@ int s3imph_sha256_file(const char *path, int portable, char hex_out[65], char *e
  *       - object_count.u64 and total_bytes.u64 are optional (Open requires them,
  *         index.go:46-56): only s3imph_index_from_objects_host (section 5d) writes them, the
  *         other builds leave them to the caller's aggregation.  Without them object_count / total_bytes read 0 and
- *         a non-zero filter returns S3IMPH_ERR_STATE.  Tier stats are out of scope.
+ *         a non-zero filter returns S3IMPH_ERR_STATE.
+       - The per-tier statistics (tiers.json + tier_stats/, section 5e) are read when present,
+         as format.OpenTierStats does; Open also checks that every tier array holds Count()
+         entries of width 8 and that the manifest's ids and file names are sane.
  *       - Open validates the values, not only the headers (the reference trusts the
  *         files): see s3imph_index_open.  No kernel is ever handed an index that could
  *         make it read out of bounds.
@@ -453,7 +456,8 @@ int s3imph_index_descendants_fill(s3imph_index *idx, uint64_t *d_out, uint64_t c
  *     and may have any byte alignment.  max_depth is NewAggregator's maxDepth (aggregator.go:25,
  *     :53): 0 = unlimited.  Row 0 is the root "" (aggregator.go:48) with every object; m == 0
  *     gives no rows (Drain returns nil).  Sums wrap like Go's uint64 +=.  The per-tier columns
- *     (TierCounts / TierBytes) are out of scope: the reader does not read them (section 5c).
+ *     (TierCounts / TierBytes) come from the *_tiers entry points of section 5e, which sit
+ *     beside the ones below; the ones below neither read nor produce them.
  * ------------------------------------------------------------------------ */
 typedef struct s3imph_agg_info {
     uint64_t n_prefixes;      /* rows, the root included */
@@ -507,6 +511,123 @@ int s3imph_aggregate_host(int device, const uint8_t *keys, const uint64_t *key_o
 int s3imph_index_from_objects_host(int device, const uint8_t *keys, const uint64_t *key_offsets,
                                    const uint64_t *sizes, uint64_t m, uint32_t max_depth, const char *out_dir,
                                    char *err, size_t errlen);
+
+/* ------------------------------------------------------------------------
+ * 5e. Per-storage-class tier statistics, from the listing to the reader: pkg/tiers
+ *     (tiers.go:16-53, :85-115, :126-170), PrefixStats.Add's TierCounts / TierBytes
+ *     (extsort/types.go:200-205), IndexBuilder.writeTierStats / writeTierManifest
+ *     (indexbuild.go:251-314, :521-533), format.OpenTierStats / GetBreakdown[All]
+ *     (tierstats.go:108-215) and Index.HasTierData / TierBreakdown* (indexread/index.go:360-399).
+ *
+ *     A tier id is a uint8_t below S3IMPH_NUM_TIERS.  Per prefix row and tier t:
+ *     count[t] = objects of tier t under the prefix, bytes[t] = the sum of their sizes
+ *     (mod 2^64).  A tier is PRESENT when some object has it (a size-0 object counts).
+ *
+ *     Files: for each present tier, in ascending id order, tier_stats/<file>_count.u64 and
+ *     tier_stats/<file>_bytes.u64 (S3ID u64 arrays of n entries), then tiers.json as
+ *     json.MarshalIndent(TierManifest, "", "  ") writes it ({"tiers": [{"id", "name", "file"}]},
+ *     no trailing newline).  The reference lists the present tiers in Go map order, which is
+ *     random; ascending id is this library's deterministic choice.  Without a present tier
+ *     (m == 0) neither tier_stats/ nor tiers.json is written.  manifest.json does not list the
+ *     tier files (WriteManifest hashes a fixed list, manifest.go:43-56).
+ * ------------------------------------------------------------------------ */
+#define S3IMPH_NUM_TIERS 12
+#define S3IMPH_TIER_STANDARD 0
+#define S3IMPH_TIER_STANDARD_IA 1
+#define S3IMPH_TIER_ONEZONE_IA 2
+#define S3IMPH_TIER_GLACIER_IR 3
+#define S3IMPH_TIER_GLACIER_FR 4
+#define S3IMPH_TIER_DEEP_ARCHIVE 5
+#define S3IMPH_TIER_REDUCED_REDUNDANCY 6
+#define S3IMPH_TIER_IT_FREQUENT 7
+#define S3IMPH_TIER_IT_INFREQUENT 8
+#define S3IMPH_TIER_IT_ARCHIVE_INSTANT 9
+#define S3IMPH_TIER_IT_ARCHIVE 10
+#define S3IMPH_TIER_IT_DEEP_ARCHIVE 11
+
+/* Mapping.FromS3 (tiers.go:85-115): both arguments trimmed of white space and upper-cased
+ * (NULL = ""); INTELLIGENT_TIERING takes its tier from access_tier (FREQUENT when that is
+ * missing or unknown); an unknown storage class is STANDARD.  Host-only, no device call. */
+int s3imph_tier_from_s3(const char *storage_class, const char *access_tier);
+/* Info.Name ("STANDARD", "GLACIER", ...) and Info.FilePrefix ("standard", "glacier_fr", ...) of
+ * tiers.go:39-53; NULL for id >= S3IMPH_NUM_TIERS. */
+const char *s3imph_tier_name(int id);
+const char *s3imph_tier_file(int id);
+
+typedef struct s3imph_agg_tier_info {
+    uint64_t present_mask;    /* bit t set iff some object has tier t (presentTiers) */
+    uint64_t first_bad_tier;  /* smallest i with d_tiers[i] >= S3IMPH_NUM_TIERS; UINT64_MAX when none */
+} s3imph_agg_tier_info;
+
+/* s3imph_aggregate_plan_device plus the tier pass over d_tiers (m tier ids, one per object):
+ * fills *tier_info as well.  A tier id >= S3IMPH_NUM_TIERS is S3IMPH_ERR_INVALID with the index
+ * in the message (in Go it would index past [MaxTiers]uint64 and panic; here it is refused) and
+ * leaves no plan.  d_tiers and d_sizes, like the keys, must stay valid and unchanged until
+ * s3imph_aggregate_fill_tiers_device has run.  Scratch: 192 / 64 = 3 bytes per object and
+ * 16 bytes per row on top of the plain plan's. */
+int s3imph_aggregate_plan_tiers_device(s3imph_ctx *ctx, const uint8_t *d_keys, const uint64_t *d_key_offsets,
+                                       const uint64_t *d_sizes, const uint8_t *d_tiers, uint64_t m,
+                                       uint32_t max_depth, s3imph_agg_info *info,
+                                       s3imph_agg_tier_info *tier_info, void *stream);
+
+/* The tier columns of the last plan's rows, after s3imph_aggregate_fill_device of that plan:
+ * S3IMPH_NUM_TIERS columns each of TierCounts and TierBytes, column t starting at element
+ * t * n_cap, its first n_prefixes entries valid, in row order; the columns of absent tiers are
+ * zeros.  d_sizes was NULL: the byte columns are zeros.  S3IMPH_ERR_STATE after a plan made
+ * without tiers or before the fill, S3IMPH_ERR_INVALID when n_cap < n_prefixes.  Synchronous on
+ * `stream`. */
+int s3imph_aggregate_fill_tiers_device(s3imph_ctx *ctx, uint64_t *d_tier_count, uint64_t *d_tier_bytes,
+                                       uint64_t n_cap, void *stream);
+
+/* s3imph_aggregate_host with `tiers` (m ids) in and, beside its five arrays, *tier_count and
+ * *tier_bytes out (S3IMPH_NUM_TIERS x *n u64 each, column t at t * *n; release with s3imph_free)
+ * and *present_mask.  m == 0: both NULL, mask 0. */
+int s3imph_aggregate_tiers_host(int device, const uint8_t *keys, const uint64_t *key_offsets, const uint64_t *sizes,
+                                const uint8_t *tiers, uint64_t m, uint32_t max_depth, uint8_t **blob,
+                                uint64_t **offsets, uint32_t **depth, uint64_t **object_count,
+                                uint64_t **total_bytes, uint64_t **tier_count, uint64_t **tier_bytes,
+                                uint64_t *present_mask, uint64_t *n, char *err, size_t errlen);
+
+/* s3imph_index_from_objects_host plus the tier files described above. */
+int s3imph_index_from_objects_tiers_host(int device, const uint8_t *keys, const uint64_t *key_offsets,
+                                         const uint64_t *sizes, const uint8_t *tiers, uint64_t m,
+                                         uint32_t max_depth, const char *out_dir, char *err, size_t errlen);
+
+/* The writer alone (host-only): tier_stats/ and tiers.json for the tiers of present_mask from
+ * column-major host arrays (column t at t * stride, n entries). */
+int s3imph_write_tier_files(const char *out_dir, uint64_t present_mask, const uint64_t *tier_count,
+                            const uint64_t *tier_bytes, uint64_t n, uint64_t stride, char *err, size_t errlen);
+
+/* Reader.  s3imph_index_open does what OpenTierStats does: no tiers.json, or an empty "tiers"
+ * list, is an index without tier data; otherwise both arrays of every listed tier are opened
+ * through the manifest's "file" field, in the manifest's order (GetBreakdown iterates it, so a
+ * reference-built index answers in its own order).  Error texts follow the reference:
+ * "open tier stats: read tier manifest: parse tier manifest: ...", "open tier stats: open <NAME>
+ * bytes: ...", "open tier stats: open <NAME> counts: ...".  Tightenings (S3IMPH_ERR_FORMAT): an
+ * array whose count is not Count() or whose width is not 8, a duplicate id, an id >=
+ * S3IMPH_NUM_TIERS, a "file" containing '/' or "..".  All on the host, before the device.
+ * In HBM the columns are interleaved by position, [n][2 T] u64 (count, bytes per manifest slot):
+ * one position's breakdown is one contiguous run of at most 192 bytes. */
+
+/* Tier data for a handle of s3imph_index_attach: T tiers with the given ids, taken from the
+ * column-major device arrays s3imph_aggregate_fill_tiers_device wrote (column ids[s] at
+ * ids[s] * stride).  The handle copies what it needs; the arrays need not outlive the call.
+ * T == 0 removes the tier data.  S3IMPH_ERR_INVALID for T > 12, a duplicate id or an id >= 12. */
+int s3imph_index_attach_tiers(s3imph_index *idx, const uint8_t *ids, uint64_t T, const uint64_t *d_tier_count,
+                              const uint64_t *d_tier_bytes, uint64_t stride);
+/* len(PresentTiers()): 0 without tier data (HasTierData() false) — tierstats.go:217-228. */
+uint64_t s3imph_index_tier_count(const s3imph_index *idx);
+/* The ids in manifest order into ids[0 .. min(cap, T)); returns T. */
+uint64_t s3imph_index_tier_ids(const s3imph_index *idx, uint8_t *ids, uint64_t cap);
+/* TierBreakdownAll / TierBreakdown (index.go:368-392; GetBreakdownAll / GetBreakdown,
+ * tierstats.go:157-215) for nq positions: d_out is nq x 2T u64, query q slot s holding the
+ * count at [q * 2T + 2s] and the bytes at [q * 2T + 2s + 1] (TierBreakdownAll); bit s of
+ * d_mask[q] (uint32_t, nq entries) is set iff either is non-zero — the set bits in slot order
+ * are TierBreakdown.  pos >= Count() (the UINT64_MAX of a failed lookup included) gives zeros
+ * and mask 0; T == 0 returns S3IMPH_OK and writes nothing.  s3imph_index_lookup_device followed
+ * by this is TierBreakdownForPrefix (index.go:394-399). */
+int s3imph_index_tiers_device(s3imph_index *idx, const uint64_t *d_qpos, uint64_t nq, uint64_t *d_out,
+                              uint32_t *d_mask, void *stream);
 
 /* ------------------------------------------------------------------------
  * 6. Deterministic synthetic prefix sets (bench/test support, not on the path).

@@ -21,6 +21,13 @@
 // each key (with block / superblock minima of c beside it); three scans turn them into row
 // bases, row byte bases and Z; the emit is partitioned by output rows and output bytes,
 // not by key, so a key of thousands of '/' is spread over as many lanes.
+//
+// Per-tier columns (include/s3imph.h section 5e; PrefixStats.Add, types.go:200-205).  With one
+// tier id per object, TierCounts[t] / TierBytes[t] of the row (i, d) are range sums over the same
+// keys [i, e): a tile pass sums counts and bytes per tier over tiles of kTG keys (one wave each),
+// one scan turns the 24 columns of tile sums into wrapping prefixes, and the emit — one lane per
+// row, adjacent lanes adjacent rows, 24 coalesced column writes — takes the whole tiles of [i, e)
+// from the table and walks the two partial tiles (fewer than 2 kTG elements, whatever e - i is).
 #include <rocprim/device/device_scan.hpp>
 
 #include <sys/stat.h>
@@ -30,6 +37,7 @@
 
 #include "s3imph_ctx.h"
 #include "s3imph_device.h"
+#include "s3imph_tiers.h"
 
 namespace s3imph {
 
@@ -48,6 +56,9 @@ constexpr int kAS = 1024;  // blocks per superblock
 constexpr int kAT = 256;   // lanes per workgroup of the emit kernels: one row / one blob word each
 constexpr uint64_t kMaxRows = 1ull << 30;  // what the MPHF build takes on one GPU
 constexpr uint32_t kMaxDepth16 = 65535;    // PrefixRow.Depth is a uint16
+constexpr int kNT = S3IMPH_NUM_TIERS;      // tiers
+constexpr int kTG = 64;                    // keys per tile of the tier prefix table: one wave
+constexpr int kTW = 4;                     // tiles (waves) per workgroup of the tile pass
 
 // What the key pass reports: the smallest unsorted index, the smallest index of a key deeper
 // than a uint16 depth, the deepest (capped) depth.
@@ -212,7 +223,9 @@ __global__ __launch_bounds__(kAT) void k_agg_bounds(const uint64_t* __restrict__
 // (upper-bound search inside the workgroup's keys, k_agg_bounds) and has depth d = c'[i] + 1 +
 // (r - rowbase[i]).  A walk over the key finds its d-th '/' and the bytes of the key's
 // earlier rows; the range end e = first index > i with c[e] < d comes from the element ->
-// block -> superblock -> back down walk of k_fin_subtree.  Row 0 is the root.
+// block -> superblock -> back down walk of k_fin_subtree.  Row 0 is the root.  kKeep (a plan with
+// tiers): the row's key range goes to rowrange[2r] = i, rowrange[2r + 1] = e for the tier emit.
+template <bool kKeep>
 __global__ __launch_bounds__(kAT) void k_agg_rows(const uint8_t* __restrict__ blob,
                                                   const uint64_t* __restrict__ koff, uint64_t m, uint32_t cap,
                                                   const uint32_t* __restrict__ c, const uint64_t* __restrict__ rowbase,
@@ -222,7 +235,8 @@ __global__ __launch_bounds__(kAT) void k_agg_rows(const uint8_t* __restrict__ bl
                                                   const uint32_t* __restrict__ smin, uint64_t nb, uint64_t nsb,
                                                   uint64_t n, uint64_t blob_bytes, uint64_t* __restrict__ offsets,
                                                   uint32_t* __restrict__ depth, uint64_t* __restrict__ ocnt,
-                                                  uint64_t* __restrict__ tbytes, uint64_t* __restrict__ rowsrc) {
+                                                  uint64_t* __restrict__ tbytes, uint64_t* __restrict__ rowsrc,
+                                                  uint64_t* __restrict__ rowrange) {
   const uint64_t base = (uint64_t)blockIdx.x * kAT;
   if (base >= n) return;
   const uint64_t end = min(n, base + kAT);
@@ -234,6 +248,10 @@ __global__ __launch_bounds__(kAT) void k_agg_rows(const uint8_t* __restrict__ bl
     ocnt[0] = m;
     tbytes[0] = Z ? Z[m] : 0;
     rowsrc[0] = 0;
+    if (kKeep) {
+      rowrange[0] = 0;
+      rowrange[1] = m;
+    }
   }
   if (end < 2) return;  // the root alone
   // the keys this workgroup's rows come from (rowbase has m + 1 entries, rowbase[0] = 1,
@@ -301,6 +319,10 @@ __global__ __launch_bounds__(kAT) void k_agg_rows(const uint8_t* __restrict__ bl
   }
   ocnt[r] = e - i;
   tbytes[r] = Z ? Z[e] - Z[i] : 0;
+  if (kKeep) {
+    rowrange[2 * r] = i;
+    rowrange[2 * r + 1] = e;
+  }
 }
 
 // Emit, by output bytes: each lane assembles one 8-byte word of prefix_blob.  The row of a byte
@@ -347,6 +369,113 @@ __global__ __launch_bounds__(kAT) void k_agg_bytes(const uint8_t* __restrict__ b
   }
 }
 
+// ---- the per-tier columns ----------------------------------------------------------------
+// What the tier pass reports: the smallest index of a tier id >= kNT, the objects of each tier.
+struct TierTop {
+  unsigned long long first_bad;
+  unsigned long long total[kNT];
+};
+
+// Tile pass: one wave per tile of kTG keys.  S is the prefix table before its scan, 2 kNT columns
+// of ntp = tiles + 1 entries: column t the tile's objects of tier t, column kNT + t the sum of
+// their sizes; entry `tiles` of every column is the zero the exclusive scan turns into the
+// column's total.  Counts are ballots; a byte sum is a wave reduction, skipped (uniformly) for
+// a tier the tile does not hold — a listing's neighbours mostly share their storage class.
+__global__ __launch_bounds__(kTG* kTW) void k_agg_tier_tiles(const uint8_t* __restrict__ tiers,
+                                                             const uint64_t* __restrict__ sizes, uint64_t m,
+                                                             uint64_t tiles, uint64_t* __restrict__ S,
+                                                             TierTop* __restrict__ top) {
+  const uint64_t tile = (uint64_t)blockIdx.x * kTW + (threadIdx.x >> 6);
+  if (tile >= tiles) return;  // whole waves leave; nothing below waits on another wave
+  const uint64_t ntp = tiles + 1;
+  const unsigned lane = lane_id();
+  const uint64_t j = tile * kTG + lane;
+  const bool valid = j < m;
+  const unsigned t = valid ? tiers[j] : 0xffu;
+  const uint64_t z = valid && sizes ? sizes[j] : 0;
+  const uint64_t bad = __ballot(valid && t >= (unsigned)kNT);
+  if (bad && lane == (unsigned)__builtin_ctzll(bad)) atomicMin(&top->first_bad, (unsigned long long)j);
+#pragma unroll
+  for (int tt = 0; tt < kNT; ++tt) {
+    const bool mine = t == (unsigned)tt;  // false for the lanes past m (0xff)
+    const uint64_t bal = __ballot(mine);
+    uint64_t v = 0;
+    if (bal && sizes) {
+      v = mine ? z : 0;
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor((unsigned long long)v, o);
+    }
+    if (lane == 0) {
+      S[(uint64_t)tt * ntp + tile] = (uint64_t)__popcll(bal);
+      S[(uint64_t)(kNT + tt) * ntp + tile] = v;
+    }
+  }
+  if (tile == tiles - 1 && lane < 2 * kNT) S[(uint64_t)lane * ntp + tiles] = 0;
+}
+
+// After the scan: the objects of each tier (its column's last entry less its first; the scan
+// runs through all columns, so a column starts at the sum of the ones before it).
+__global__ void k_agg_tier_totals(const uint64_t* __restrict__ T, uint64_t ntp, TierTop* __restrict__ top) {
+  const unsigned t = threadIdx.x;
+  if (t < (unsigned)kNT) top->total[t] = T[(uint64_t)t * ntp + ntp - 1] - T[(uint64_t)t * ntp];
+}
+
+// Emit: one lane per row, adjacent lanes adjacent rows, so each of the 24 column writes is
+// coalesced.  The row covers the keys [i, e): its whole tiles come from the prefix table T
+// (differences inside one column, so the column's starting value cancels mod 2^64), the partial
+// tiles at both ends are walked — fewer than 2 kTG elements for any e - i, and e - i itself for a
+// row inside one tile.  An element's tier is matched against all kNT accumulators with selects
+// (registers, no dynamic indexing); the columns of absent tiers come out as the zeros they are.
+__global__ __launch_bounds__(kAT) void k_agg_tier_emit(const uint8_t* __restrict__ tiers,
+                                                       const uint64_t* __restrict__ sizes,
+                                                       const uint64_t* __restrict__ T, uint64_t ntp,
+                                                       const uint64_t* __restrict__ rowrange, uint64_t n,
+                                                       uint64_t n_cap, uint64_t* __restrict__ cnt_out,
+                                                       uint64_t* __restrict__ bytes_out) {
+  const uint64_t r = (uint64_t)blockIdx.x * kAT + threadIdx.x;
+  if (r >= n) return;
+  const uint64_t i = rowrange[2 * r], e = rowrange[2 * r + 1];
+  uint32_t c[kNT];  // walked objects per tier: fewer than 2 kTG
+  uint64_t b[kNT];
+#pragma unroll
+  for (int t = 0; t < kNT; ++t) {
+    c[t] = 0;
+    b[t] = 0;
+  }
+  auto walk = [&](uint64_t lo, uint64_t hi) {
+    for (uint64_t j = lo; j < hi; ++j) {
+      const unsigned tj = tiers[j];
+      const uint64_t z = sizes ? sizes[j] : 0;
+#pragma unroll
+      for (int t = 0; t < kNT; ++t) {
+        const bool mine = tj == (unsigned)t;
+        c[t] += mine ? 1u : 0u;
+        b[t] += mine ? z : 0;
+      }
+    }
+  };
+  const uint64_t ti = i / kTG, te = e / kTG;  // te <= tiles = ntp - 1
+  const bool whole = ti != te;                // the row has whole tiles (or at least a tile edge) inside
+  if (!whole) {
+    walk(i, e);
+  } else {
+    walk(i, (ti + 1) * kTG);
+    walk(te * kTG, e);
+  }
+#pragma unroll
+  for (int t = 0; t < kNT; ++t) {
+    uint64_t cc = c[t], bb = b[t];
+    if (whole) {
+      const uint64_t* Tc = T + (uint64_t)t * ntp;
+      const uint64_t* Tb = T + (uint64_t)(kNT + t) * ntp;
+      cc += Tc[te] - Tc[ti + 1];
+      bb += Tb[te] - Tb[ti + 1];
+    }
+    cnt_out[(uint64_t)t * n_cap + r] = cc;
+    bytes_out[(uint64_t)t * n_cap + r] = bb;
+  }
+}
+
 }  // namespace
 
 // Scratch of the aggregation and the last plan, kept in the context and grown as needed.
@@ -362,8 +491,19 @@ struct AggScratch {
   uint64_t bounds_cap = 0;
   void* tmp = nullptr;
   size_t tmp_cap = 0;
+  // the tier columns: the prefix table (2 kNT columns of tiles + 1 entries), what the tile pass
+  // reports, each row's key range [i, e) (kept by the fill of a plan with tiers)
+  uint64_t* ttab = nullptr;
+  uint64_t ttab_cap = 0;
+  TierTop* ttop = nullptr;
+  uint64_t* rowrange = nullptr;
+  uint64_t range_cap = 0;
   // the last plan
   bool have_plan = false, sized = false;
+  bool tiered = false, ranges_kept = false;  // planned with tiers; its fill has run
+  const uint8_t* tiers = nullptr;
+  const uint64_t* sizes = nullptr;
+  uint64_t present_mask = 0;
   const uint8_t* keys = nullptr;
   const uint64_t* koff = nullptr;
   uint64_t m = 0, n = 0, blob_bytes = 0, key_end8 = 0;
@@ -379,7 +519,10 @@ struct AggScratch {
     dfree(rowsrc);
     dfree(bounds);
     dfree(tmp);
-    cap = rows_cap = bounds_cap = 0;
+    dfree(ttab);
+    dfree(ttop);
+    dfree(rowrange);
+    cap = rows_cap = bounds_cap = ttab_cap = range_cap = 0;
     tmp_cap = 0;
     have_plan = false;
   }
@@ -419,6 +562,7 @@ int aggregate_plan(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, con
   if (!c->agg) c->agg = new AggScratch();
   AggScratch& a = *c->agg;
   a.have_plan = false;
+  a.tiered = a.ranges_kept = false;
   if (m == 0) {
     a.keys = nullptr;
     a.koff = nullptr;
@@ -512,6 +656,7 @@ int aggregate_fill(s3imph_ctx* c, uint8_t* blob, uint64_t blob_cap, uint64_t* of
   if (a.n == 0) {
     HIPCHECK(hipMemsetAsync(offsets, 0, 8, s));
     HIPCHECK(hipStreamSynchronize(s));
+    a.ranges_kept = a.tiered;
     return S3IMPH_OK;
   }
   if (a.n > a.rows_cap) {
@@ -528,15 +673,105 @@ int aggregate_fill(s3imph_ctx* c, uint8_t* blob, uint64_t blob_cap, uint64_t* of
     a.bounds_cap = std::max(rchunks, wchunks);
   }
   k_agg_bounds<<<(unsigned)((rchunks + kAT - 1) / kAT), kAT, 0, s>>>(a.rowbase, a.m + 1, kAT, 1, rchunks, a.bounds);
-  k_agg_rows<<<(unsigned)rchunks, kAT, 0, s>>>(a.keys, a.koff, a.m, a.depth_cap, a.c, a.rowbase, a.keybytes, a.bounds,
-                                               a.sized ? a.Z : nullptr, a.bmin, a.smin, nb, nsb, a.n, a.blob_bytes,
-                                               offsets, depth, ocnt, tbytes, a.rowsrc);
+  if (a.tiered) {
+    if (a.n > a.range_cap) {
+      a.range_cap = 0;
+      dalloc(a.rowrange, 2 * a.n);
+      a.range_cap = a.n;
+    }
+    k_agg_rows<true><<<(unsigned)rchunks, kAT, 0, s>>>(a.keys, a.koff, a.m, a.depth_cap, a.c, a.rowbase, a.keybytes,
+                                                       a.bounds, a.sized ? a.Z : nullptr, a.bmin, a.smin, nb, nsb, a.n,
+                                                       a.blob_bytes, offsets, depth, ocnt, tbytes, a.rowsrc,
+                                                       a.rowrange);
+  } else {
+    k_agg_rows<false><<<(unsigned)rchunks, kAT, 0, s>>>(a.keys, a.koff, a.m, a.depth_cap, a.c, a.rowbase, a.keybytes,
+                                                        a.bounds, a.sized ? a.Z : nullptr, a.bmin, a.smin, nb, nsb, a.n,
+                                                        a.blob_bytes, offsets, depth, ocnt, tbytes, a.rowsrc, nullptr);
+  }
   if (nw) {
     k_agg_bounds<<<(unsigned)((wchunks + kAT - 1) / kAT), kAT, 0, s>>>(offsets, a.n + 1, 8ull * kAT, 0, wchunks,
                                                                       a.bounds);
     k_agg_bytes<<<(unsigned)wchunks, kAT, 0, s>>>(a.keys, a.key_end8, offsets, a.rowsrc, a.bounds, a.n, a.blob_bytes,
                                                   blob);
   }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(s));
+  a.ranges_kept = a.tiered;
+  return S3IMPH_OK;
+}
+
+// Plan with tiers: the plain plan, then the tile pass over (tiers, sizes) and the scan of its
+// table; fills *tinfo.  Waits for the stream.
+int aggregate_plan_tiers(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes,
+                         const uint8_t* tiers, uint64_t m, uint32_t max_depth, s3imph_agg_info* info,
+                         s3imph_agg_tier_info* tinfo, hipStream_t s, std::string* msg) {
+  tinfo->present_mask = 0;
+  tinfo->first_bad_tier = UINT64_MAX;
+  const int rc = aggregate_plan(c, keys, koff, sizes, m, max_depth, info, s, msg);
+  if (rc != S3IMPH_OK) return rc;
+  AggScratch& a = *c->agg;
+  a.have_plan = false;  // until the tiers are known to be good
+  a.tiers = tiers;
+  a.sizes = sizes;
+  a.present_mask = 0;
+  if (m) {
+    const uint64_t tiles = (m + kTG - 1) / kTG, ntp = tiles + 1;
+    if (2 * kNT * ntp > a.ttab_cap) {
+      a.ttab_cap = 0;
+      dalloc(a.ttab, 2 * kNT * ntp);
+      a.ttab_cap = 2 * kNT * ntp;
+    }
+    if (!a.ttop) dalloc(a.ttop, 1);
+    TierTop top;
+    std::memset(&top, 0, sizeof top);
+    top.first_bad = ~0ull;
+    HIPCHECK(hipMemcpyAsync(a.ttop, &top, sizeof top, hipMemcpyHostToDevice, s));
+    k_agg_tier_tiles<<<(unsigned)((tiles + kTW - 1) / kTW), kTG * kTW, 0, s>>>(tiers, sizes, m, tiles, a.ttab, a.ttop);
+    HIPCHECK(hipGetLastError());
+    scan_u64(a, a.ttab, 2 * kNT * ntp, 0, s);
+    k_agg_tier_totals<<<1, 64, 0, s>>>(a.ttab, ntp, a.ttop);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(&top, a.ttop, sizeof top, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    tinfo->first_bad_tier = top.first_bad;
+    if (top.first_bad != ~0ull) {
+      *msg = "aggregate: object " + std::to_string(top.first_bad) + " has a tier id of " +
+             std::to_string(S3IMPH_NUM_TIERS) + " or more";
+      return S3IMPH_ERR_INVALID;
+    }
+    for (int t = 0; t < kNT; ++t)
+      if (top.total[t]) a.present_mask |= 1ull << t;
+  }
+  tinfo->present_mask = a.present_mask;
+  a.tiered = true;
+  a.have_plan = true;
+  return S3IMPH_OK;
+}
+
+// The tier columns of the last plan's rows (after its fill).  Waits for the stream.
+int aggregate_fill_tiers(s3imph_ctx* c, uint64_t* tcount, uint64_t* tbytes, uint64_t n_cap, hipStream_t s,
+                         std::string* msg) {
+  if (!c->agg || !c->agg->have_plan || !c->agg->tiered) {
+    *msg = "aggregate: tier fill without a plan that had tiers";
+    return S3IMPH_ERR_STATE;
+  }
+  AggScratch& a = *c->agg;
+  if (!a.ranges_kept) {
+    *msg = "aggregate: tier fill before the fill of the rows";
+    return S3IMPH_ERR_STATE;
+  }
+  if (n_cap < a.n) {
+    *msg = "aggregate: the plan needs " + std::to_string(a.n) + " rows per tier column";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (a.n == 0) return S3IMPH_OK;
+  if (!tcount || !tbytes) {
+    *msg = "aggregate: null output array";
+    return S3IMPH_ERR_INVALID;
+  }
+  const uint64_t tiles = (a.m + kTG - 1) / kTG;
+  k_agg_tier_emit<<<(unsigned)((a.n + kAT - 1) / kAT), kAT, 0, s>>>(a.tiers, a.sizes, a.ttab, tiles + 1, a.rowrange, a.n,
+                                                                   n_cap, tcount, tbytes);
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(s));
   return S3IMPH_OK;
@@ -571,13 +806,17 @@ struct DevRows {
   uint8_t* blob = nullptr;
   uint64_t *offsets = nullptr, *ocnt = nullptr, *tbytes = nullptr;
   uint32_t* depth = nullptr;
+  // with tiers: kNT columns of n entries each, the present tiers
+  uint64_t *tier_count = nullptr, *tier_bytes = nullptr;
+  uint64_t present_mask = 0;
 };
 
-// H2D of the listing, plan, fill; the listing's device copy is freed before returning.
+// H2D of the listing, plan, fill (with `tiers`: the tier forms and the tier columns too); the
+// listing's device copy is freed before returning.
 int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes,
-                   uint64_t m, uint32_t max_depth, DevRows* out, std::string* msg) {
+                   uint64_t m, uint32_t max_depth, DevRows* out, std::string* msg, const uint8_t* tiers = nullptr) {
   hipStream_t s = c->own_stream;
-  uint8_t* d_keys = nullptr;
+  uint8_t *d_keys = nullptr, *d_tiers = nullptr;
   uint64_t *d_koff = nullptr, *d_sizes = nullptr;
   if (m) {
     const uint64_t b0 = koff[0], nbytes = koff[m] - b0;
@@ -589,9 +828,15 @@ int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64
       g.make(d_sizes, m);
       staged_copy(c, true, d_sizes, sizes, m * 8);
     }
+    if (tiers) {
+      g.make(d_tiers, m);
+      HIPCHECK(hipMemcpy(d_tiers, tiers, m, hipMemcpyHostToDevice));
+    }
   }
   s3imph_agg_info info;
-  int rc = aggregate_plan(c, d_keys, d_koff, d_sizes, m, max_depth, &info, s, msg);
+  s3imph_agg_tier_info tinfo;
+  int rc = tiers ? aggregate_plan_tiers(c, d_keys, d_koff, d_sizes, d_tiers, m, max_depth, &info, &tinfo, s, msg)
+                 : aggregate_plan(c, d_keys, d_koff, d_sizes, m, max_depth, &info, s, msg);
   if (rc != S3IMPH_OK) return rc;
   out->n = info.n_prefixes;
   out->blob_bytes = info.blob_bytes;
@@ -602,10 +847,17 @@ int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64
   g.make(out->tbytes, out->n);
   rc = aggregate_fill(c, out->blob, (info.blob_bytes + 7) & ~7ull, out->offsets, out->depth, out->ocnt, out->tbytes,
                       out->n, s, msg);
+  if (rc == S3IMPH_OK && tiers) {
+    out->present_mask = tinfo.present_mask;
+    g.make(out->tier_count, kNT * out->n);
+    g.make(out->tier_bytes, kNT * out->n);
+    rc = aggregate_fill_tiers(c, out->tier_count, out->tier_bytes, out->n, s, msg);
+  }
   c->agg->have_plan = false;  // the listing's copy goes away with this call
   g.drop(d_keys);
   g.drop(d_koff);
   g.drop(d_sizes);
+  g.drop(d_tiers);
   return rc;
 }
 
@@ -634,6 +886,44 @@ bool is_dir(const std::string& p) {
 using namespace s3imph;
 
 extern "C" {
+
+int s3imph_aggregate_plan_tiers_device(s3imph_ctx* c, const uint8_t* d_keys, const uint64_t* d_key_offsets,
+                                       const uint64_t* d_sizes, const uint8_t* d_tiers, uint64_t m,
+                                       uint32_t max_depth, s3imph_agg_info* info, s3imph_agg_tier_info* tier_info,
+                                       void* stream) {
+  if (!c || !info || !tier_info || (m && (!d_keys || !d_key_offsets || !d_tiers))) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  std::string msg;
+  try {
+    HIPCHECK(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
+    const int rc = retry_on_nomem(c, s, &msg, [&] {
+      return aggregate_plan_tiers(c, d_keys, d_key_offsets, d_sizes, d_tiers, m, max_depth, info, tier_info, s, &msg);
+    });
+    c->last_msg = msg;
+    return rc;
+  } catch (const Fail& f) {
+    c->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+int s3imph_aggregate_fill_tiers_device(s3imph_ctx* c, uint64_t* d_tier_count, uint64_t* d_tier_bytes, uint64_t n_cap,
+                                       void* stream) {
+  if (!c) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(c->mu);
+  std::string msg;
+  try {
+    HIPCHECK(hipSetDevice(c->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
+    const int rc = aggregate_fill_tiers(c, d_tier_count, d_tier_bytes, n_cap, s, &msg);
+    c->last_msg = msg;
+    return rc;
+  } catch (const Fail& f) {
+    c->last_msg = f.msg;
+    return f.code;
+  }
+}
 
 int s3imph_aggregate_plan_device(s3imph_ctx* c, const uint8_t* d_keys, const uint64_t* d_key_offsets,
                                  const uint64_t* d_sizes, uint64_t m, uint32_t max_depth, s3imph_agg_info* info,
@@ -674,15 +964,27 @@ int s3imph_aggregate_fill_device(s3imph_ctx* c, uint8_t* d_blob, uint64_t blob_c
   }
 }
 
-int s3imph_aggregate_host(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
-                          uint64_t m, uint32_t max_depth, uint8_t** blob, uint64_t** offsets, uint32_t** depth,
-                          uint64_t** object_count, uint64_t** total_bytes, uint64_t* n, char* err, size_t errlen) {
+// s3imph_aggregate_host, and with `tiers` s3imph_aggregate_tiers_host (tier_count, tier_bytes and
+// present_mask are then given).
+static int aggregate_host_impl(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
+                               const uint8_t* tiers, uint64_t m, uint32_t max_depth, uint8_t** blob,
+                               uint64_t** offsets, uint32_t** depth, uint64_t** object_count, uint64_t** total_bytes,
+                               uint64_t** tier_count, uint64_t** tier_bytes, uint64_t* present_mask, uint64_t* n,
+                               char* err, size_t errlen) {
   if (!blob || !offsets || !depth || !object_count || !total_bytes || !n || !listing_given(keys, key_offsets, m))
     return S3IMPH_ERR_INVALID;
+  uint64_t *no_count = nullptr, *no_bytes = nullptr, no_mask = 0;
+  if (!tiers) {
+    tier_count = &no_count;
+    tier_bytes = &no_bytes;
+    present_mask = &no_mask;
+  }
   *blob = nullptr;
   *offsets = nullptr;
   *depth = nullptr;
   *object_count = *total_bytes = nullptr;
+  *tier_count = *tier_bytes = nullptr;
+  *present_mask = 0;
   *n = 0;
   std::string msg;
   auto drop = [&] {
@@ -691,10 +993,13 @@ int s3imph_aggregate_host(int device, const uint8_t* keys, const uint64_t* key_o
     std::free(*depth);
     std::free(*object_count);
     std::free(*total_bytes);
+    std::free(*tier_count);
+    std::free(*tier_bytes);
     *blob = nullptr;
     *offsets = nullptr;
     *depth = nullptr;
     *object_count = *total_bytes = nullptr;
+    *tier_count = *tier_bytes = nullptr;
   };
   try {
     if (m == 0) {  // Drain returns nil
@@ -712,7 +1017,7 @@ int s3imph_aggregate_host(int device, const uint8_t* keys, const uint64_t* key_o
     const int rc = retry_on_nomem(c, c->own_stream, &msg, [&] {
       DevGuard g;
       DevRows r;
-      const int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg);
+      const int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers);
       if (rc2 != S3IMPH_OK) return rc2;
       drop();
       *blob = host_array<uint8_t>(r.blob_bytes);
@@ -725,6 +1030,13 @@ int s3imph_aggregate_host(int device, const uint8_t* keys, const uint64_t* key_o
       staged_copy(c, false, *depth, r.depth, r.n * 4);
       staged_copy(c, false, *object_count, r.ocnt, r.n * 8);
       staged_copy(c, false, *total_bytes, r.tbytes, r.n * 8);
+      if (tiers) {
+        *tier_count = host_array<uint64_t>(kNT * r.n);
+        *tier_bytes = host_array<uint64_t>(kNT * r.n);
+        staged_copy(c, false, *tier_count, r.tier_count, kNT * r.n * 8);
+        staged_copy(c, false, *tier_bytes, r.tier_bytes, kNT * r.n * 8);
+        *present_mask = r.present_mask;
+      }
       *n = r.n;
       return (int)S3IMPH_OK;
     });
@@ -747,8 +1059,27 @@ int s3imph_aggregate_host(int device, const uint8_t* keys, const uint64_t* key_o
   }
 }
 
-int s3imph_index_from_objects_host(int device, const uint8_t* keys, const uint64_t* key_offsets,
-                                   const uint64_t* sizes, uint64_t m, uint32_t max_depth, const char* out_dir,
+int s3imph_aggregate_host(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
+                          uint64_t m, uint32_t max_depth, uint8_t** blob, uint64_t** offsets, uint32_t** depth,
+                          uint64_t** object_count, uint64_t** total_bytes, uint64_t* n, char* err, size_t errlen) {
+  return aggregate_host_impl(device, keys, key_offsets, sizes, nullptr, m, max_depth, blob, offsets, depth,
+                             object_count, total_bytes, nullptr, nullptr, nullptr, n, err, errlen);
+}
+
+int s3imph_aggregate_tiers_host(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
+                                const uint8_t* tiers, uint64_t m, uint32_t max_depth, uint8_t** blob,
+                                uint64_t** offsets, uint32_t** depth, uint64_t** object_count, uint64_t** total_bytes,
+                                uint64_t** tier_count, uint64_t** tier_bytes, uint64_t* present_mask, uint64_t* n,
+                                char* err, size_t errlen) {
+  static const uint8_t kNone = 0;
+  if (!tier_count || !tier_bytes || !present_mask || (m && !tiers)) return S3IMPH_ERR_INVALID;
+  return aggregate_host_impl(device, keys, key_offsets, sizes, tiers ? tiers : &kNone, m, max_depth, blob, offsets,
+                             depth, object_count, total_bytes, tier_count, tier_bytes, present_mask, n, err, errlen);
+}
+
+// s3imph_index_from_objects_host, and with `tiers` s3imph_index_from_objects_tiers_host.
+static int index_from_objects_impl(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
+                                   const uint8_t* tiers, uint64_t m, uint32_t max_depth, const char* out_dir,
                                    char* err, size_t errlen) {
   if (!out_dir || !listing_given(keys, key_offsets, m)) return S3IMPH_ERR_INVALID;
   const std::string dir = out_dir;
@@ -761,7 +1092,8 @@ int s3imph_index_from_objects_host(int device, const uint8_t* keys, const uint64
     uint64_t n = 0;
     uint32_t md = 0;
     std::vector<uint8_t> mph, blob;
-    std::vector<uint64_t> fp, pos, offs, send, dpos, doff, ocnt, tbytes;
+    std::vector<uint64_t> fp, pos, offs, send, dpos, doff, ocnt, tbytes, tcount, tcbytes;
+    uint64_t present_mask = 0;
     std::vector<uint32_t> depth, maxds;
     if (m) {
       s3imph_ctx* c = default_ctx(device, &msg);
@@ -776,9 +1108,21 @@ int s3imph_index_from_objects_host(int device, const uint8_t* keys, const uint64
       const int rc = retry_on_nomem(c, s, &msg, [&]() -> int {
         DevGuard g;
         DevRows r;
-        int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg);
+        int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers);
         if (rc2 != S3IMPH_OK) return rc2;
         n = r.n;
+        if (tiers) {  // the columns of the present tiers leave HBM before the build needs the room
+          present_mask = r.present_mask;
+          tcount.resize(kNT * n);
+          tcbytes.resize(kNT * n);
+          for (int t = 0; t < kNT; ++t) {
+            if (!((present_mask >> t) & 1)) continue;
+            staged_copy(c, false, tcount.data() + t * n, r.tier_count + t * n, n * 8);
+            staged_copy(c, false, tcbytes.data() + t * n, r.tier_bytes + t * n, n * 8);
+          }
+          g.drop(r.tier_count);
+          g.drop(r.tier_bytes);
+        }
         uint64_t *d_fp = nullptr, *d_pos = nullptr, *d_send = nullptr, *d_dpos = nullptr, *d_doff = nullptr;
         uint32_t *d_depth = nullptr, *d_maxds = nullptr;
         g.make(d_fp, n);
@@ -840,6 +1184,7 @@ int s3imph_index_from_objects_host(int device, const uint8_t* keys, const uint64
       rc = write_finalize_files(dir, depth.data(), send.data(), maxds.data(), doff.data(), doff.size(), dpos.data(), n,
                                 &msg);
     if (rc == S3IMPH_OK) rc = write_stats_files(dir, ocnt.data(), tbytes.data(), n, &msg);
+    if (rc == S3IMPH_OK && tiers) rc = write_tier_files(dir, present_mask, tcount.data(), tcbytes.data(), n, n, &msg);
     if (rc == S3IMPH_OK) rc = write_manifest(dir, n, md, &msg);
     if (rc != S3IMPH_OK) set_err(err, errlen, msg);
     return rc;
@@ -850,6 +1195,21 @@ int s3imph_index_from_objects_host(int device, const uint8_t* keys, const uint64
     set_err(err, errlen, "aggregate: out of host memory");
     return S3IMPH_ERR_NOMEM;
   }
+}
+
+int s3imph_index_from_objects_host(int device, const uint8_t* keys, const uint64_t* key_offsets,
+                                   const uint64_t* sizes, uint64_t m, uint32_t max_depth, const char* out_dir,
+                                   char* err, size_t errlen) {
+  return index_from_objects_impl(device, keys, key_offsets, sizes, nullptr, m, max_depth, out_dir, err, errlen);
+}
+
+int s3imph_index_from_objects_tiers_host(int device, const uint8_t* keys, const uint64_t* key_offsets,
+                                         const uint64_t* sizes, const uint8_t* tiers, uint64_t m, uint32_t max_depth,
+                                         const char* out_dir, char* err, size_t errlen) {
+  static const uint8_t kNone = 0;
+  if (m && !tiers) return S3IMPH_ERR_INVALID;
+  return index_from_objects_impl(device, keys, key_offsets, sizes, tiers ? tiers : &kNone, m, max_depth, out_dir, err,
+                                 errlen);
 }
 
 }  // extern "C"

@@ -7,7 +7,9 @@
 //   Lookup / StatsForPrefix    index.go:128-152;
 //   Stats / Depth / SubtreeEnd / MaxDepthInSubtree   index.go:135-176;
 //   DescendantsAtDepth[Filtered] / DescendantsUpToDepth   index.go:206-297, over
-//   GetPositionsInSubtree (depthindex.go:193-259, two binary searches in a depth's slice).
+//   GetPositionsInSubtree (depthindex.go:193-259, two binary searches in a depth's slice);
+//   HasTierData / TierBreakdown / TierBreakdownAll / TierBreakdownForPrefix   index.go:360-399,
+//   over OpenTierStats / GetBreakdown[All] (tierstats.go:108-215; include/s3imph.h section 5e).
 //
 // GPU formulation.  A batch of descendants queries is a CSR: `levels` per query, `row_ptr`
 // over the result rows, and the flat list of positions.  The plan step runs one lane per
@@ -28,6 +30,7 @@
 
 #include "s3imph_ctx.h"
 #include "s3imph_device.h"
+#include "s3imph_tiers.h"
 
 namespace s3imph {
 namespace {
@@ -67,6 +70,53 @@ __global__ __launch_bounds__(kQT) void k_index_nodes(IndexArrays a, const uint64
     r.found = 1;
   }
   out[i] = r;
+}
+
+// TierBreakdownAll / TierBreakdown (tierstats.go:157-215) for one (query, manifest slot) per
+// lane.  The tier table is interleaved by position, tier[(p * T + s) * 2] = count and
+// [.. + 1] = bytes of slot s, so the T lanes of a query read one contiguous run of 16 T bytes
+// and write one.  A workgroup takes qb = kQT / T whole queries; their masks are gathered in LDS.
+__global__ __launch_bounds__(kQT) void k_index_tiers(const uint64_t* __restrict__ tier, uint64_t n, uint32_t T,
+                                                     uint32_t qb, const uint64_t* __restrict__ qpos, uint64_t nq,
+                                                     uint64_t* __restrict__ out, uint32_t* __restrict__ mask) {
+  __shared__ unsigned s_mask[kQT];
+  s_mask[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t ql = threadIdx.x / T, s = threadIdx.x - ql * T;
+  const uint64_t q = (uint64_t)blockIdx.x * qb + ql;
+  const bool active = ql < qb && q < nq;
+  if (active) {
+    const uint64_t p = qpos[q];
+    uint64_t c = 0, b = 0;
+    if (p < n) {
+      const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(tier + (p * T + s) * 2);
+      c = v.x;
+      b = v.y;
+    }
+    out[(q * T + s) * 2] = c;
+    out[(q * T + s) * 2 + 1] = b;
+    if (c | b) atomicOr(&s_mask[ql], 1u << s);
+  }
+  __syncthreads();
+  if (active && s == 0) mask[q] = s_mask[ql];
+}
+
+struct TierSlots {
+  uint8_t id[S3IMPH_NUM_TIERS];
+};
+
+// The interleaved table from the column-major arrays of the aggregation (column t at
+// t * stride): one lane per position, reads coalesced along each column.
+__global__ __launch_bounds__(kQT) void k_tier_interleave(const uint64_t* __restrict__ cnt,
+                                                         const uint64_t* __restrict__ bytes, uint64_t stride,
+                                                         uint64_t n, uint32_t T, TierSlots ids,
+                                                         uint64_t* __restrict__ out) {
+  const uint64_t p = (uint64_t)blockIdx.x * kQT + threadIdx.x;
+  if (p >= n) return;
+  for (uint32_t s = 0; s < T; ++s) {
+    const uint64_t col = (uint64_t)ids.id[s] * stride + p;
+    *reinterpret_cast<ulonglong2*>(out + (p * T + s) * 2) = make_ulonglong2(cnt[col], bytes[col]);
+  }
 }
 
 // One lane per result row: the row's slice start in depth_positions and its unfiltered
@@ -440,10 +490,58 @@ bool mph_bin_framed(const uint8_t* p, uint64_t len, uint64_t* keys, std::string*
 struct HostIndex {
   HostArray send, depth, mds, doff, dpos, fp, pos, ocnt, tbytes;
   bool stats = false;
+  std::vector<TierEntry> tiers;     // tiers.json's entries, in its order (none: no tier data)
+  std::vector<uint64_t> tier_table;  // [n][2 T]: count, bytes per manifest slot
   std::vector<uint8_t> mph;
   uint64_t n = 0;
   uint32_t max_depth = 0;
 };
+
+// OpenTierStats (tierstats.go:108-146) for an index of n nodes: tiers.json's entries and both
+// arrays of each, interleaved by position into h->tier_table.
+int load_host_tiers(const std::string& dir, uint64_t n, HostIndex* h, std::string* msg) {
+  std::string m;
+  int rc = read_tier_manifest(dir, &h->tiers, &m);
+  if (rc != S3IMPH_OK) {
+    *msg = "open tier stats: " + m;
+    return rc;
+  }
+  const uint64_t T = h->tiers.size();
+  if (T == 0) return S3IMPH_OK;  // no tiers.json, or an empty list: no tier data
+  auto refuse = [&](const std::string& what) {
+    *msg = "open tier stats: read tier manifest: " + what;
+    return (int)S3IMPH_ERR_FORMAT;
+  };
+  unsigned seen = 0;
+  for (const TierEntry& e : h->tiers) {
+    if (e.id >= (unsigned)S3IMPH_NUM_TIERS)
+      return refuse("tier id " + std::to_string(e.id) + " is not below " + std::to_string(S3IMPH_NUM_TIERS));
+    if ((seen >> e.id) & 1) return refuse("tier id " + std::to_string(e.id) + " is listed twice");
+    seen |= 1u << e.id;
+    if (e.file.empty() || e.file.find('/') != std::string::npos || e.file.find("..") != std::string::npos)
+      return refuse("file \"" + e.file + "\" of tier " + std::to_string(e.id) + " is not a plain file prefix");
+  }
+  h->tier_table.assign(n * 2 * T, 0);
+  for (uint64_t s = 0; s < T; ++s) {
+    const TierEntry& e = h->tiers[s];
+    for (int k = 0; k < 2; ++k) {  // the bytes array first, as the reference opens them
+      const char* what = k ? " counts: " : " bytes: ";
+      HostArray a;
+      rc = read_array(dir + "/tier_stats/" + e.file + (k ? "_count.u64" : "_bytes.u64"), 8, &a, &m);
+      if (rc == S3IMPH_OK && a.count != n) {
+        m = "holds " + std::to_string(a.count) + " entries, subtree_end " + std::to_string(n);
+        rc = S3IMPH_ERR_FORMAT;
+      }
+      if (rc != S3IMPH_OK) {
+        *msg = "open tier stats: open " + e.name + what + m;
+        return rc;
+      }
+      const uint64_t* v = a.u64();
+      for (uint64_t p = 0; p < n; ++p) h->tier_table[(p * T + s) * 2 + (k ? 0 : 1)] = v[p];
+    }
+  }
+  return S3IMPH_OK;
+}
 
 int load_host_index(const std::string& dir, HostIndex* h, std::string* msg) {
   std::string m;
@@ -553,7 +651,7 @@ int load_host_index(const std::string& dir, HostIndex* h, std::string* msg) {
       m = "mph_pos[" + std::to_string(i) + "] is not a node";
       return fail("open MPHF", S3IMPH_ERR_FORMAT);
     }
-  return S3IMPH_OK;
+  return load_host_tiers(dir, n, h, msg);
 }
 
 }  // namespace
@@ -570,6 +668,11 @@ struct s3imph_index {
   std::string last_msg;
   IndexArrays a;
   std::vector<void*> owned;  // device allocations of Open
+  // tier data (Open, or s3imph_index_attach_tiers): T manifest slots, their ids, the table
+  // [n][2 T] in HBM (owned either way)
+  uint32_t T = 0;
+  uint8_t tier_ids[S3IMPH_NUM_TIERS] = {};
+  uint64_t* tier_table = nullptr;
   // workspace of the last plan: per row the slice start, the unfiltered length and the
   // unfiltered row_ptr U (rows + 1); scan block sums; per chunk the flag counts and their prefix
   uint64_t *row_lo = nullptr, *row_len = nullptr, *U = nullptr, *sums = nullptr;
@@ -590,7 +693,8 @@ void index_free(s3imph_index* x) {
   if (x->ctx) (void)s3imph_ctx_destroy(x->ctx);  // drains its stream first
   for (void* p : x->owned)
     if (p) (void)hipFree(p);
-  for (uint64_t** p : {&x->row_lo, &x->row_len, &x->U, &x->sums, &x->csum, &x->cbase, &x->csums2}) dfree(*p);
+  for (uint64_t** p : {&x->row_lo, &x->row_len, &x->U, &x->sums, &x->csum, &x->cbase, &x->csums2, &x->tier_table})
+    dfree(*p);
   delete x;
 }
 
@@ -765,6 +869,13 @@ int s3imph_index_open(int device, const char* dir, s3imph_index** out, char* err
         x->a.ocnt = upload(x, h.ocnt.u64(), h.n);
         x->a.tbytes = upload(x, h.tbytes.u64(), h.n);
       }
+      if (!h.tiers.empty()) {
+        dalloc(x->tier_table, h.tier_table.size());
+        if (!h.tier_table.empty())
+          HIPCHECK(hipMemcpy(x->tier_table, h.tier_table.data(), h.tier_table.size() * 8, hipMemcpyHostToDevice));
+        x->T = (uint32_t)h.tiers.size();
+        for (uint32_t k = 0; k < x->T; ++k) x->tier_ids[k] = (uint8_t)h.tiers[k].id;
+      }
     } catch (const Fail& f) {
       index_free(x);
       set_err(err, errlen, f.msg);
@@ -842,6 +953,80 @@ int s3imph_index_nodes_device(s3imph_index* x, const uint64_t* d_qpos, uint64_t 
     HIPCHECK(hipSetDevice(x->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
     k_index_nodes<<<(unsigned)((nq + kQT - 1) / kQT), kQT, 0, s>>>(x->a, d_qpos, nq, d_out);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
+    return S3IMPH_OK;
+  } catch (const Fail& f) {
+    x->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+int s3imph_index_attach_tiers(s3imph_index* x, const uint8_t* ids, uint64_t T, const uint64_t* d_tier_count,
+                              const uint64_t* d_tier_bytes, uint64_t stride) {
+  if (!x) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(x->mu);
+  x->last_msg.clear();
+  unsigned seen = 0;
+  bool ok = T <= (uint64_t)S3IMPH_NUM_TIERS && (T == 0 || ids) && stride >= x->a.n &&
+            (T == 0 || x->a.n == 0 || (d_tier_count && d_tier_bytes));
+  for (uint64_t k = 0; ok && k < T; ++k) {
+    ok = ids[k] < S3IMPH_NUM_TIERS && !((seen >> ids[k]) & 1);
+    seen |= 1u << (ids[k] & 31);
+  }
+  if (!ok) {
+    x->last_msg = "attach tiers: invalid argument";
+    return S3IMPH_ERR_INVALID;
+  }
+  try {
+    HIPCHECK(hipSetDevice(x->device));
+    hipStream_t s = x->ctx->own_stream;
+    x->T = 0;
+    dfree(x->tier_table);
+    if (T == 0) return S3IMPH_OK;
+    dalloc(x->tier_table, x->a.n * 2 * T);
+    TierSlots slots{};
+    for (uint64_t k = 0; k < T; ++k) slots.id[k] = ids[k];
+    if (x->a.n) {
+      k_tier_interleave<<<(unsigned)((x->a.n + kQT - 1) / kQT), kQT, 0, s>>>(d_tier_count, d_tier_bytes, stride, x->a.n,
+                                                                            (uint32_t)T, slots, x->tier_table);
+      HIPCHECK(hipGetLastError());
+      HIPCHECK(hipStreamSynchronize(s));
+    }
+    std::memcpy(x->tier_ids, slots.id, sizeof slots.id);
+    x->T = (uint32_t)T;
+    return S3IMPH_OK;
+  } catch (const Fail& f) {
+    x->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+uint64_t s3imph_index_tier_count(const s3imph_index* x) { return x ? x->T : 0; }
+
+uint64_t s3imph_index_tier_ids(const s3imph_index* x, uint8_t* ids, uint64_t cap) {
+  if (!x) return 0;
+  for (uint64_t k = 0; ids && k < x->T && k < cap; ++k) ids[k] = x->tier_ids[k];
+  return x->T;
+}
+
+int s3imph_index_tiers_device(s3imph_index* x, const uint64_t* d_qpos, uint64_t nq, uint64_t* d_out, uint32_t* d_mask,
+                              void* stream) {
+  if (!x) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(x->mu);
+  x->last_msg.clear();
+  if (x->T == 0 || nq == 0) return S3IMPH_OK;  // no tier data: nothing is written
+  if (!d_qpos || !d_out || !d_mask) return S3IMPH_ERR_INVALID;
+  try {
+    HIPCHECK(hipSetDevice(x->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+    const uint32_t qb = kQT / x->T;
+    const uint64_t blocks = (nq + qb - 1) / qb;
+    if (blocks > 0x7fffffffull) {
+      x->last_msg = "tier breakdown: more than 2^31 workgroups of queries in one batch";
+      return S3IMPH_ERR_INVALID;
+    }
+    k_index_tiers<<<(unsigned)blocks, kQT, 0, s>>>(x->tier_table, x->a.n, x->T, qb, d_qpos, nq, d_out, d_mask);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     return S3IMPH_OK;

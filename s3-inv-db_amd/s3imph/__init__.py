@@ -14,7 +14,9 @@ plus the device-resident API that bench.py times (``DeviceBuilder``), the
 multi-GPU rank API (``DistBuilder``), the batched lookup (``MPHF``), the reader,
 ``Index`` (indexread.Index: Open / Lookup / Stats / Descendants* over a batch), and the front
 of the pipeline: ``aggregate`` (extsort.Aggregator + SortPrefixRows: object listing -> prefix
-rows) and ``build_index_from_objects`` (object listing -> index directory).
+rows) and ``build_index_from_objects`` (object listing -> index directory).  With one tier id
+per object (``TIERS``, ``tier_from_s3``) both also carry the per-storage-class statistics that
+``Index.tier_breakdown*`` answer from.
 
 Every compute call goes through the HIP library; there is no CPU fallback.
 If libs3imph.so is missing, importing this module raises.
@@ -75,7 +77,12 @@ EXPORTS = (
     "s3imph_index_nodes_device", "s3imph_index_descendants_plan", "s3imph_index_descendants_fill",
     "s3imph_aggregate_plan_device", "s3imph_aggregate_fill_device", "s3imph_aggregate_host",
     "s3imph_index_from_objects_host",
+    "s3imph_tier_from_s3", "s3imph_tier_name", "s3imph_tier_file",
+    "s3imph_aggregate_plan_tiers_device", "s3imph_aggregate_fill_tiers_device", "s3imph_aggregate_tiers_host",
+    "s3imph_index_from_objects_tiers_host", "s3imph_write_tier_files",
+    "s3imph_index_attach_tiers", "s3imph_index_tier_count", "s3imph_index_tier_ids", "s3imph_index_tiers_device",
 )
+NUM_TIERS = 12  # S3IMPH_NUM_TIERS
 
 
 class MPHFError(RuntimeError):
@@ -133,6 +140,11 @@ class AggInfo(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
+class AggTierInfo(ctypes.Structure):
+    """s3imph_agg_tier_info: what a plan with tiers found (include/s3imph.h, section 5e)."""
+    _fields_ = [("present_mask", ctypes.c_uint64), ("first_bad_tier", ctypes.c_uint64)]
 
 
 # s3imph_node: what Index.nodes returns, one record per queried position
@@ -208,6 +220,20 @@ def _load():
         "s3imph_aggregate_host": (i32, [i32, vp, vp, vp, u64, ctypes.c_uint32, P(vp), P(vp), P(vp), P(vp), P(vp),
                                         P(u64), cp, sz]),
         "s3imph_index_from_objects_host": (i32, [i32, vp, vp, vp, u64, ctypes.c_uint32, cp, cp, sz]),
+        "s3imph_tier_from_s3": (i32, [cp, cp]),
+        "s3imph_tier_name": (cp, [i32]),
+        "s3imph_tier_file": (cp, [i32]),
+        "s3imph_aggregate_plan_tiers_device": (i32, [vp, vp, vp, vp, vp, u64, ctypes.c_uint32, P(AggInfo),
+                                                     P(AggTierInfo), vp]),
+        "s3imph_aggregate_fill_tiers_device": (i32, [vp, vp, vp, u64, vp]),
+        "s3imph_aggregate_tiers_host": (i32, [i32, vp, vp, vp, vp, u64, ctypes.c_uint32, P(vp), P(vp), P(vp), P(vp),
+                                              P(vp), P(vp), P(vp), P(u64), P(u64), cp, sz]),
+        "s3imph_index_from_objects_tiers_host": (i32, [i32, vp, vp, vp, vp, u64, ctypes.c_uint32, cp, cp, sz]),
+        "s3imph_write_tier_files": (i32, [cp, u64, vp, vp, u64, u64, cp, sz]),
+        "s3imph_index_attach_tiers": (i32, [vp, vp, u64, vp, vp, u64]),
+        "s3imph_index_tier_count": (u64, [vp]),
+        "s3imph_index_tier_ids": (u64, [vp, vp, u64]),
+        "s3imph_index_tiers_device": (i32, [vp, vp, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -221,6 +247,36 @@ LIB = _load()
 # read by the library only after this opt-in; the tests and tools/gpu.sh set S3IMPH_DEV=1.
 if os.environ.get("S3IMPH_DEV") == "1":
     LIB.s3imph_dev_knobs(1)
+
+
+# tiers.AllTiers (pkg/tiers/tiers.go:39-53): (id, name, file prefix), from the library's table
+TIERS = tuple((t, LIB.s3imph_tier_name(t).decode(), LIB.s3imph_tier_file(t).decode()) for t in range(NUM_TIERS))
+
+
+def tier_from_s3(storage_class: str, access_tier: str = "") -> int:
+    """Mapping.FromS3 (tiers.go:85-115): an inventory row's StorageClass and
+    IntelligentTieringAccessTier -> tier id."""
+    return int(LIB.s3imph_tier_from_s3((storage_class or "").encode(), (access_tier or "").encode()))
+
+
+def _tier_ids(tiers, m: int) -> np.ndarray:
+    t = np.ascontiguousarray(tiers, np.uint8)
+    if t.shape != (m,):
+        raise ValueError("tiers must hold one id per key")
+    return t
+
+
+def write_tier_files(out_dir: str, present_mask: int, tier_count: np.ndarray, tier_bytes: np.ndarray) -> None:
+    """s3imph_write_tier_files: tier_stats/ and tiers.json for the tiers of present_mask from
+    (NUM_TIERS, n) u64 arrays; nothing for an empty mask."""
+    tc = np.ascontiguousarray(tier_count, np.uint64).reshape(NUM_TIERS, -1)
+    tb = np.ascontiguousarray(tier_bytes, np.uint64).reshape(NUM_TIERS, -1)
+    n = tc.shape[1]
+    if tb.shape != tc.shape:
+        raise ValueError("tier_count and tier_bytes must have the same shape")
+    err = ctypes.create_string_buffer(1024)
+    _check(LIB.s3imph_write_tier_files(os.fsencode(out_dir), present_mask, ctypes.c_void_p(tc.ctypes.data),
+                                       ctypes.c_void_p(tb.ctypes.data), n, n, err, 1024), err)
 
 
 def dev_knobs(on: bool = True) -> None:
@@ -504,16 +560,29 @@ class DeviceBuilder:
         return {"depth": depth[:n], "subtree_end": send[:n], "max_depth_in_subtree": mds[:n],
                 "depth_positions": dpos[:n], "depth_offsets": doff[: md.value + 2], "max_depth": md.value}
 
-    def aggregate_plan(self, d_keys, d_key_offsets, m: int, d_sizes=None, max_depth: int = 0, stream=None) -> dict:
+    def aggregate_plan(self, d_keys, d_key_offsets, m: int, d_sizes=None, max_depth: int = 0, stream=None,
+                       tiers=None) -> dict:
         """s3imph_aggregate_plan_device: size the prefix rows of a byte-sorted object listing in
         HBM (AddObject over every key, aggregator.go:44-61).  Returns s3imph_agg_info as a dict
         (n_prefixes, blob_bytes, n_objects, total_bytes, first_unsorted, max_depth_seen); a
         refusal raises MPHFError with that dict as ``.info``.  The key tensors must stay valid
-        and unchanged until aggregate_fill."""
+        and unchanged until aggregate_fill.  With ``tiers`` (a uint8 device tensor, one tier id per
+        key) it is s3imph_aggregate_plan_tiers_device: the dict gains present_mask and
+        first_bad_tier, and tiers / d_sizes must stay valid until aggregate_fill_tiers."""
         info = AggInfo()
-        rc = LIB.s3imph_aggregate_plan_device(self._h, _dev_ptr(d_keys), _dev_ptr(d_key_offsets), _dev_ptr(d_sizes),
-                                              m, max_depth, ctypes.byref(info), _stream_ptr(stream))
-        self.last_agg = info.as_dict()
+        if tiers is None:
+            rc = LIB.s3imph_aggregate_plan_device(self._h, _dev_ptr(d_keys), _dev_ptr(d_key_offsets),
+                                                  _dev_ptr(d_sizes), m, max_depth, ctypes.byref(info),
+                                                  _stream_ptr(stream))
+            self.last_agg = info.as_dict()
+        else:
+            tinfo = AggTierInfo()
+            rc = LIB.s3imph_aggregate_plan_tiers_device(self._h, _dev_ptr(d_keys), _dev_ptr(d_key_offsets),
+                                                        _dev_ptr(d_sizes), _dev_ptr(tiers), m, max_depth,
+                                                        ctypes.byref(info), ctypes.byref(tinfo), _stream_ptr(stream))
+            self.last_agg = info.as_dict()
+            self.last_agg["present_mask"] = int(tinfo.present_mask)
+            self.last_agg["first_bad_tier"] = int(tinfo.first_bad_tier)
         if rc != OK:
             e = MPHFError(rc, self.last_error() or f"aggregate: {status_string(rc)}")
             e.info = self.last_agg
@@ -542,6 +611,25 @@ class DeviceBuilder:
             raise MPHFError(rc, self.last_error() or f"aggregate: {status_string(rc)}")
         return {"blob": blob[: (nbytes + 7) // 8 * 8], "offsets": offs[: n + 1], "depth": depth[:n],
                 "object_count": ocnt[:n], "total_bytes": tbytes[:n], "n": n, "blob_bytes": nbytes}
+
+    def aggregate_fill_tiers(self, n_cap: int | None = None, device=None, stream=None) -> dict:
+        """s3imph_aggregate_fill_tiers_device: the tier columns of the last plan's rows, after
+        aggregate_fill: tier_count / tier_bytes as (NUM_TIERS, n_cap) int64 tensors holding the
+        u64 bits (row t = TierCounts[t] / TierBytes[t] of every prefix row; [:, :n] is valid),
+        n, present_mask."""
+        import torch
+        info = getattr(self, "last_agg", None) or {"n_prefixes": 0}
+        n = info["n_prefixes"]
+        n_cap = n if n_cap is None else n_cap
+        dev = f"cuda:{self.device}" if device is None else device
+        tc = torch.empty((NUM_TIERS, max(n_cap, 1)), dtype=torch.int64, device=dev)
+        tb = torch.empty((NUM_TIERS, max(n_cap, 1)), dtype=torch.int64, device=dev)
+        # the column stride is the tensors' row length (n_cap, or 1 for an empty result)
+        rc = LIB.s3imph_aggregate_fill_tiers_device(self._h, _dev_ptr(tc), _dev_ptr(tb), n_cap if n_cap else 0,
+                                                    _stream_ptr(stream))
+        if rc != OK:
+            raise MPHFError(rc, self.last_error() or f"aggregate: {status_string(rc)}")
+        return {"tier_count": tc, "tier_bytes": tb, "n": n, "present_mask": info.get("present_mask", 0)}
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -579,17 +667,26 @@ def _listing(keys_blob, key_offsets, sizes):
 
 
 def aggregate(keys_blob: np.ndarray, key_offsets: np.ndarray, sizes: np.ndarray | None, max_depth: int = 0,
-              device: int = 0):
+              device: int = 0, tiers=None):
     """extsort.Aggregator + SortPrefixRows (aggregator.go:44-76, :138-) on the GPU
     (s3imph_aggregate_host): the byte-sorted object listing (keys in the blob / offsets layout,
     one size per key; max_depth 0 = unlimited) -> (prefix_blob u8, prefix_offsets u64[n + 1],
-    depth u32[n], object_count u64[n], total_bytes u64[n]) in the reference's row order."""
+    depth u32[n], object_count u64[n], total_bytes u64[n]) in the reference's row order.  With
+    ``tiers`` (one tier id per key; s3imph_aggregate_tiers_host) the tuple gains tier_count and
+    tier_bytes, (NUM_TIERS, n) u64 each, and present_mask."""
     blob, offs, sz, m = _listing(keys_blob, key_offsets, sizes)
-    out = [ctypes.c_void_p() for _ in range(5)]
+    out = [ctypes.c_void_p() for _ in range(5 if tiers is None else 7)]
     n = ctypes.c_uint64()
+    mask = ctypes.c_uint64()
     err = ctypes.create_string_buffer(1024)
-    rc = LIB.s3imph_aggregate_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), m, max_depth,
-                                   *[ctypes.byref(p) for p in out], ctypes.byref(n), err, 1024)
+    if tiers is None:
+        rc = LIB.s3imph_aggregate_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), m, max_depth,
+                                       *[ctypes.byref(p) for p in out], ctypes.byref(n), err, 1024)
+    else:
+        tr = _tier_ids(tiers, m)
+        rc = LIB.s3imph_aggregate_tiers_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), _np_ptr(tr), m,
+                                             max_depth, *[ctypes.byref(p) for p in out], ctypes.byref(mask),
+                                             ctypes.byref(n), err, 1024)
     try:
         _check(rc, err)
         nn = n.value
@@ -601,8 +698,12 @@ def aggregate(keys_blob: np.ndarray, key_offsets: np.ndarray, sizes: np.ndarray 
             return a
 
         offsets = take(out[1], np.uint64, nn + 1)
-        return (take(out[0], np.uint8, int(offsets[-1])), offsets, take(out[2], np.uint32, nn),
+        rows = (take(out[0], np.uint8, int(offsets[-1])), offsets, take(out[2], np.uint32, nn),
                 take(out[3], np.uint64, nn), take(out[4], np.uint64, nn))
+        if tiers is None:
+            return rows
+        return rows + (take(out[5], np.uint64, NUM_TIERS * nn).reshape(NUM_TIERS, nn),
+                       take(out[6], np.uint64, NUM_TIERS * nn).reshape(NUM_TIERS, nn), int(mask.value))
     finally:
         for p in out:
             if p.value:
@@ -610,14 +711,20 @@ def aggregate(keys_blob: np.ndarray, key_offsets: np.ndarray, sizes: np.ndarray 
 
 
 def build_index_from_objects(keys_blob: np.ndarray, key_offsets: np.ndarray, sizes: np.ndarray | None, out_dir: str,
-                             max_depth: int = 0, device: int = 0) -> None:
+                             max_depth: int = 0, device: int = 0, tiers=None) -> None:
     """Object listing in, index directory out (s3imph_index_from_objects_host): aggregation,
     MPHF build and finalize in one device residency; writes the MPHF-stage files, the finalize
-    files, object_count.u64 / total_bytes.u64 and manifest.json into out_dir."""
+    files, object_count.u64 / total_bytes.u64 and manifest.json into out_dir.  With ``tiers`` (one
+    tier id per key; s3imph_index_from_objects_tiers_host) also tier_stats/ and tiers.json."""
     blob, offs, sz, m = _listing(keys_blob, key_offsets, sizes)
     err = ctypes.create_string_buffer(1024)
-    _check(LIB.s3imph_index_from_objects_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), m, max_depth,
-                                              os.fsencode(out_dir), err, 1024), err)
+    if tiers is None:
+        _check(LIB.s3imph_index_from_objects_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), m, max_depth,
+                                                  os.fsencode(out_dir), err, 1024), err)
+    else:
+        tr = _tier_ids(tiers, m)
+        _check(LIB.s3imph_index_from_objects_tiers_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), _np_ptr(tr),
+                                                        m, max_depth, os.fsencode(out_dir), err, 1024), err)
 
 
 def write_manifest(out_dir: str, node_count: int, max_depth: int) -> None:
@@ -746,6 +853,10 @@ class Index:
         idx.descendants_at_depth(pos, rel)        # DescendantsAtDepth[Filtered] (:206, :277)
         idx.descendants_up_to_depth(pos, max_rel) # DescendantsUpToDepth (:239)
         idx.prefix_string(pos)                    # PrefixString (:179)
+        idx.has_tier_data(), idx.present_tiers()  # HasTierData (:360), the manifest's tiers
+        idx.tier_breakdown_all(pos)               # TierBreakdownAll (:380)
+        idx.tier_breakdown(pos)                   # TierBreakdown (:368)
+        idx.tier_breakdown_for_prefix(keys)       # TierBreakdownForPrefix (:394)
         idx.close()                               # Close (:108)
 
     Positions are given as a sequence, a numpy array or a device tensor (int64 holding the
@@ -794,6 +905,65 @@ class Index:
         self._init(device, None, (fp, pos, depth, subtree_end, max_depth_in_subtree, depth_offsets, depth_positions,
                                   object_count, total_bytes))
         return self
+
+    attach = from_arrays  # s3imph_index_attach under its own name
+
+    def attach_tiers(self, ids, tier_count, tier_bytes) -> None:
+        """s3imph_index_attach_tiers: tier data for a handle of from_arrays, from the
+        (NUM_TIERS, stride) device tensors DeviceBuilder.aggregate_fill_tiers returned; ``ids``
+        are the tiers to answer for, in result order (a present_mask's set bits, usually).  The
+        handle copies what it needs."""
+        ids = np.ascontiguousarray(ids, np.uint8).reshape(-1)
+        stride = int(tier_count.stride(0)) if tier_count.dim() == 2 else int(tier_count.numel()) // NUM_TIERS
+        self._fail(LIB.s3imph_index_attach_tiers(self._h, _np_ptr(ids), len(ids), _dev_ptr(tier_count),
+                                                 _dev_ptr(tier_bytes), stride), "attach tiers")
+
+    # -- tier statistics ------------------------------------------------------------------
+    def has_tier_data(self) -> bool:
+        """HasTierData (index.go:360)."""
+        return int(LIB.s3imph_index_tier_count(self._h)) > 0
+
+    def present_tiers(self) -> list:
+        """The tier ids the index holds, in manifest order (TierStatsReader.PresentTiers)."""
+        ids = np.zeros(NUM_TIERS, np.uint8)
+        t = int(LIB.s3imph_index_tier_ids(self._h, _np_ptr(ids), NUM_TIERS))
+        return [int(v) for v in ids[:t]]
+
+    def tiers_device(self, pos, stream=None):
+        """s3imph_index_tiers_device: (out int64 (nq, T, 2) holding count, bytes as u64 bits; mask
+        int32 (nq,)) on the device; T == 0 gives empty tensors."""
+        import torch
+        d_pos = self._pos_dev(pos)
+        nq, t = int(d_pos.shape[0]), int(LIB.s3imph_index_tier_count(self._h))
+        out = torch.zeros((max(nq, 1), max(t, 1), 2), dtype=torch.int64, device=self.dev)
+        mask = torch.zeros(max(nq, 1), dtype=torch.int32, device=self.dev)
+        self._fail(LIB.s3imph_index_tiers_device(self._h, _dev_ptr(d_pos), nq, _dev_ptr(out), _dev_ptr(mask),
+                                                 _stream_ptr(stream)), "tier breakdown")
+        return out[:nq, :t], mask[:nq]
+
+    def tier_breakdown_all(self, pos) -> list:
+        """TierBreakdownAll (index.go:380; GetBreakdownAll, tierstats.go:189) per position: a list
+        of (tier id, tier name, bytes, object count) for every tier of the index, in manifest
+        order (zeros past the end of the index); [] without tier data."""
+        ids = self.present_tiers()
+        out, _ = self.tiers_device(pos)
+        v = out.cpu().numpy().view(np.uint64)
+        return [[(t, TIERS[t][1], int(v[q, s, 1]), int(v[q, s, 0])) for s, t in enumerate(ids)]
+                for q in range(v.shape[0])]
+
+    def tier_breakdown(self, pos) -> list:
+        """TierBreakdown (index.go:368; GetBreakdown, tierstats.go:157): as tier_breakdown_all,
+        keeping only the tiers with a non-zero count or bytes at the position."""
+        ids = self.present_tiers()
+        out, mask = self.tiers_device(pos)
+        v, mk = out.cpu().numpy().view(np.uint64), mask.cpu().numpy().view(np.uint32)
+        return [[(t, TIERS[t][1], int(v[q, s, 1]), int(v[q, s, 0])) for s, t in enumerate(ids) if (mk[q] >> s) & 1]
+                for q in range(v.shape[0])]
+
+    def tier_breakdown_for_prefix(self, keys) -> list:
+        """TierBreakdownForPrefix (index.go:394) per key: tier_breakdown at the key's position,
+        [] for a key the index does not hold."""
+        return self.tier_breakdown(self.lookup_device(*self._keys_dev(*keys_to_blob(keys))))
 
     def last_error(self) -> str:
         return LIB.s3imph_index_last_error(self._h).decode(errors="replace")

@@ -11,6 +11,11 @@ chunks, then copied to the host for (c).
   (a) plan + fill, device-resident: objects/s, and key bytes/s
         against a device-to-device copy of the key blob (bytes/s; the pass reads every key
         twice, so half the copy's rate is its bound)
+  (a, --tiers) plan + fill + fill_tiers with one tier id per object, hash(index) % 12 (every tile
+        of the tier pass holds all 12 tiers: the worst case for its reductions), beside the plain
+        plan + fill of the same run and beside a bound from (a)'s copy: the tier pass reads 9 bytes
+        per object, the emit writes 192 bytes per row, at the rate the copy moves bytes (it reads
+        and writes the blob, so twice its key bytes/s)
   (b) DeviceBuilder.finalize_index on the same key blob: its key pass does the same per-byte
         work (count '/', lcp with the neighbour) and is the yardstick; the call also runs the
         subtree pass and the depth radix sort, so it is an upper bound on the key pass
@@ -25,7 +30,7 @@ All device calls wait for their stream, so the host clock around a call times th
 plus its launches; each figure is the median of --reps calls after --warmup.  Prints one JSON
 line per listing size.
 
-    python tools/aggregate_bench.py [--objects 10000000,100000000] [--per 4] [--reps 10]
+    python tools/aggregate_bench.py [--objects 10000000,100000000] [--per 4] [--reps 10] [--tiers]
 """
 import argparse
 import json
@@ -142,6 +147,43 @@ def run(a, s3imph, torch, m):
         res["a_baseline_copy_ms"] = [1e3 * tc, 1e3 * clo, 1e3 * chi]
         del dst
 
+    if a.tiers:
+        with section("(a, --tiers) plan + fill + fill_tiers", a.limit):
+            idx = torch.arange(m, dtype=torch.int64, device=dev)
+            d_tiers = (((idx * 2654435761) >> 11) % 12).to(torch.uint8)  # hash(index) % 12
+            del idx
+            tinfo = ctx.aggregate_plan(d_keys, d_offs, m, d_sizes, tiers=d_tiers)
+            ctx.aggregate_fill()
+            ctx.aggregate_fill_tiers()
+            assert tinfo["n_prefixes"] == n and tinfo["present_mask"] == 0xfff
+            ttp, _, _ = median_s(lambda: ctx.aggregate_plan(d_keys, d_offs, m, d_sizes, tiers=d_tiers), a.warmup, a.reps)
+            ttf, _, _ = median_s(lambda: ctx.aggregate_fill(), a.warmup, a.reps)
+            ttt, tlo, thi = median_s(lambda: ctx.aggregate_fill_tiers(), a.warmup, a.reps)
+            moved = 9 * m + 192 * n                  # the tier pass's reads + the emit's writes
+            bound = moved / (2 * nbytes / tc)        # at the bytes/s the copy moves (read + write)
+            extra = ttp + ttf + ttt - (tp + tf)
+            res["t_plan_ms"], res["t_fill_ms"] = 1e3 * ttp, 1e3 * ttf
+            res["t_fill_tiers_ms"] = [1e3 * ttt, 1e3 * tlo, 1e3 * thi]
+            res["t_total_ms"] = 1e3 * (ttp + ttf + ttt)
+            res["t_plain_total_ms"] = 1e3 * (tp + tf)
+            res["t_ratio_to_plain"] = (ttp + ttf + ttt) / (tp + tf)
+            res["t_extra_ms"] = 1e3 * extra
+            res["t_bound_bytes"] = moved
+            res["t_bound_ms"] = 1e3 * bound
+            res["t_extra_ratio_to_bound"] = extra / bound
+            res["t_objects_per_s"] = m / (ttp + ttf + ttt)
+            # the plain path after a tiers plan: what section (a) measured, measured again
+            tp2, p2lo, p2hi = median_s(lambda: ctx.aggregate_plan(d_keys, d_offs, m, d_sizes), a.warmup, a.reps)
+            tf2, f2lo, f2hi = median_s(lambda: ctx.aggregate_fill(), a.warmup, a.reps)
+            res["t_plain_again_ms"] = {"plan": [1e3 * tp2, 1e3 * p2lo, 1e3 * p2hi],
+                                       "fill": [1e3 * tf2, 1e3 * f2lo, 1e3 * f2hi]}
+            del d_tiers
+        rows = ctx.aggregate_fill()
+
+    if a.only_a:
+        ctx.close()
+        return res, None
+
     with section("(b) finalize_index on the same key blob", a.limit):
         tz, zlo, zhi = median_s(lambda: ctx.finalize_index(d_keys, d_offs, m), a.warmup, a.reps)
         res["b_finalize_index_ms"] = [1e3 * tz, 1e3 * zlo, 1e3 * zhi]
@@ -187,6 +229,8 @@ def main():
     ap.add_argument("--limit", type=int, default=240, help="seconds per section")
     ap.add_argument("--tmp", default=None, help="where (c) writes its directory")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--tiers", action="store_true", help="also time the per-tier columns (a, --tiers)")
+    ap.add_argument("--only-a", action="store_true", help="stop after section (a) (and --tiers)")
     a = ap.parse_args()
     assert 1 <= a.per <= 10
 
@@ -199,6 +243,8 @@ def main():
         res, listing = run(a, s3imph, torch, m)
         print(json.dumps(res), flush=True)
         host = host or listing
+    if host is None:
+        return
 
     with section("(d) the Python dict restatement, one thread", a.limit):
         import aggregate_ref as R

@@ -8,6 +8,11 @@ arrays built on the GPU, random object_count / total_bytes, attached with Index.
 
   (a) lookup + nodes (StatsForPrefix) for 1M member prefixes, queries/s
         against MPHF.Lookup alone (s3imph_lookup_device, what the library had before)
+  (a, tiers) the batched tier breakdown (TierBreakdownAll + TierBreakdown's mask, 12 tiers) for the
+        same 1M positions, queries/s and GB/s of table read + result written,
+        against nodes_device on those positions, and against the same answer gathered from
+        column-major columns ([12][n] counts and bytes, torch.index_select: 24 scattered 8-byte
+        loads per query) — the layout the interleaved [n][2T] table replaces
   (b) DescendantsAtDepth at rel = 1 for 1M random positions, queries/s, plan and fill apart
         against the numpy searchsorted restatement on the host (on --host-queries of them);
         C2's nodes below the root are leaves, so these rows are empty: the same positions at
@@ -145,6 +150,43 @@ def main():
         res["a_lookup_nodes_ms"] = [1e3 * t, 1e3 * lo, 1e3 * hi]
         res["a_baseline_mphf_lookup_qps"] = nq / tb_
         res["a_baseline_mphf_lookup_ms"] = [1e3 * tb_, 1e3 * blo, 1e3 * bhi]
+
+    with section("(a, tiers) tier breakdown of the same 1M positions", a.limit):
+        g = torch.Generator(device=dev)
+        g.manual_seed(11)
+        d_tc = torch.randint(0, 1 << 40, (12, n), dtype=torch.int64, device=dev, generator=g)
+        d_tbt = torch.randint(0, 1 << 50, (12, n), dtype=torch.int64, device=dev, generator=g)
+        d_tc[:, ::3] = 0
+        d_tbt[:, ::3] = 0
+        idx.attach_tiers(list(range(12)), d_tc, d_tbt)
+        d_mpos = torch.from_numpy(members.astype(np.uint64).view(np.int64)).to(dev)
+        out, mask = idx.tiers_device(d_mpos)
+        assert torch.equal(out[:, :, 0], d_tc[:, d_mpos].T) and torch.equal(out[:, :, 1], d_tbt[:, d_mpos].T)
+        assert torch.equal(mask.cpu() != 0, torch.from_numpy(members % 3 != 0))
+        del out, mask
+
+        def tiers():
+            return idx.tiers_device(d_mpos)
+
+        def nodes():
+            return idx.nodes_device(d_mpos)
+
+        def column_major():
+            r = torch.index_select(d_tc, 1, d_mpos), torch.index_select(d_tbt, 1, d_mpos)
+            torch.cuda.synchronize()
+            return r
+
+        tt, tlo, thi = median_s(tiers, a.warmup, a.reps)
+        tn, nlo, nhi = median_s(nodes, a.warmup, a.reps)
+        tcm, clo, chi = median_s(column_major, a.warmup, a.reps)
+        res["a_tiers_qps"] = nq / tt
+        res["a_tiers_ms"] = [1e3 * tt, 1e3 * tlo, 1e3 * thi]
+        res["a_tiers_gbps"] = 1e-9 * nq * (2 * 192 + 8 + 4) / tt
+        res["a_tiers_baseline_nodes_ms"] = [1e3 * tn, 1e3 * nlo, 1e3 * nhi]
+        res["a_tiers_ratio_to_nodes"] = tt / tn
+        res["a_tiers_column_major_gather_ms"] = [1e3 * tcm, 1e3 * clo, 1e3 * chi]
+        res["a_tiers_ratio_to_column_major"] = tt / tcm
+        del d_tc, d_tbt
 
     with section("(b) DescendantsAtDepth rel = 1, 1M random positions", a.limit):
         qpos = rng.integers(0, n, nq).astype(np.uint64)
