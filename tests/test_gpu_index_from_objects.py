@@ -30,15 +30,11 @@ def listing(m=20_000, seed=5):
     return keys, sizes
 
 
-@pytest.fixture(scope="module")
-def built(tmp_path_factory, oracle_lib):
-    """The GPU-built directory, the oracle-written one for the reference rows, the rows."""
-    keys, sizes = listing()
+def _build_both(keys, sizes, got, want, oracle_lib):
+    """The GPU-built directory `got`, the oracle-written one `want` for the reference rows, the rows."""
     rows = R.aggregate_dict(keys, sizes)
     blob, offs = O.keys_to_blob(keys)
-    got = tmp_path_factory.mktemp("from_objects")
     s3imph.build_index_from_objects(blob, offs, sizes, str(got))
-    want = tmp_path_factory.mktemp("from_oracle")
     prefixes = [r[0] for r in rows]
     count = np.array([r[2] for r in rows], np.uint64)
     total = np.array([r[3] for r in rows], np.uint64)
@@ -47,7 +43,34 @@ def built(tmp_path_factory, oracle_lib):
     return {"got": got, "want": want, "rows": rows, "keys": keys, "arr": arr, "count": count, "total": total}
 
 
+@pytest.fixture(scope="module")
+def built(tmp_path_factory, oracle_lib):
+    keys, sizes = listing()
+    return _build_both(keys, sizes, tmp_path_factory.mktemp("from_objects"), tmp_path_factory.mktemp("from_oracle"),
+                       oracle_lib)
+
+
 def test_directory_equals_the_oracle_written_one(built):
+    _directories_equal(built)
+
+
+def test_one_object_100_directories_deep(tmp_path_factory, oracle_lib):
+    """One object key with 100 '/': maxDepth 100 is beyond the 64 depth_offsets entries the
+    finalize of the rows is offered first, so the listing-to-directory path takes its retry."""
+    keys, sizes = listing(m=2000, seed=6)
+    deep = b"d20/" + b"x/" * 99 + b"obj"
+    assert deep.count(b"/") == 100 and deep not in keys
+    keys = sorted(keys + [deep])
+    sizes = np.concatenate([sizes, np.array([12345], np.uint64)])
+    b = _build_both(keys, sizes, tmp_path_factory.mktemp("deep_objects"), tmp_path_factory.mktemp("deep_oracle"),
+                    oracle_lib)
+    assert b["arr"]["max_depth"] == 100 and len(b["arr"]["depth_offsets"]) == 102
+    _directories_equal(b)
+    with s3imph.Index(str(b["got"])) as idx:
+        assert idx.count == len(b["rows"]) and idx.max_depth == 100
+
+
+def _directories_equal(built):
     names = sorted(os.listdir(built["want"]))
     assert sorted(os.listdir(built["got"])) == names and "object_count.u64" in names and len(names) == 13
     for name in names:
