@@ -630,6 +630,72 @@ int s3imph_index_tiers_device(s3imph_index *idx, const uint64_t *d_qpos, uint64_
                               uint32_t *d_mask, void *stream);
 
 /* ------------------------------------------------------------------------
+ * 5f. An object listing in ANY order: the order the reference makes after the fact.
+ *     Aggregator.AddObject (pkg/extsort/aggregator.go:44-76) accumulates into a map in whatever
+ *     order the objects arrive, and SortPrefixRows (pkg/extsort/types.go:160-164) sorts
+ *     afterwards; section 5d instead wants the listing byte-sorted.  The entry points below make
+ *     that order on the GPU, so an S3 inventory (which is not sorted by key) needs no host sort.
+ *
+ *     Order: keys compare as unsigned bytes and a proper prefix comes before its extensions —
+ *     Go's string <, what sort.Slice in SortPrefixRows uses; embedded 0x00 and bytes >= 0x80 are
+ *     ordinary bytes.  The sort is stable: equal keys keep their input order.
+ *     The input contract is section 5d's: the key blob on the device is readable up to
+ *     round_up(offsets[m], 8), may have any byte alignment, and offsets[0] need not be 0.
+ *     m >= 2^32 is S3IMPH_ERR_INVALID before any device work (the order is a uint32_t); null
+ *     arguments likewise.  m == 0 is OK everywhere (no order, offsets_out = [0]); m == 1 is
+ *     the identity.
+ *
+ *     Memory: the sort's scratch lives in ctx, grows on demand and is 48 bytes per object (two
+ *     packed and two word buffers, a scan, the positions, two segment tables) plus the radix
+ *     sort's temporary; a listing found sorted takes none.  The gather is out of place: the
+ *     input and the output listing — keys, offsets, sizes, tiers — coexist in HBM, so the
+ *     listing's footprint is doubled until the caller frees the input.
+ * ------------------------------------------------------------------------ */
+typedef struct s3imph_sort_info {
+    uint64_t n_objects;       /* m */
+    uint64_t key_bytes;       /* offsets[m] - offsets[0] */
+    uint64_t first_unsorted;  /* of the INPUT, as in s3imph_agg_info; UINT64_MAX: it was sorted, order = identity */
+    uint64_t n_equal;         /* sorted neighbours holding equal keys */
+    uint32_t rounds;          /* refinement rounds run (0 for sorted input); reported, not contractual */
+    uint32_t pad;
+} s3imph_sort_info;           /* 40 bytes */
+
+/* The order SortPrefixRows' comparison gives the object keys (aggregator.go:44-76 takes them in
+ * any order, types.go:160-164 sorts): d_order[j] (m entries) = the input index of the j-th key
+ * in sorted order; fills *info.  Sorted input is found by a first pass and answered with the
+ * identity.  Message of a failure: s3imph_ctx_last_error ("sort: ...").  Synchronous on `stream`. */
+int s3imph_sort_objects_device(s3imph_ctx *ctx, const uint8_t *d_keys, const uint64_t *d_key_offsets,
+                               uint64_t m, uint32_t *d_order, s3imph_sort_info *info, void *stream);
+
+/* The listing put into the order d_order (aggregator.go:44-76, types.go:160-164: what the
+ * reference's map + sort leave): d_keys_out (keys_cap >= round_up(key_bytes, 8) bytes, else
+ * S3IMPH_ERR_INVALID; the padding is written as zeros), d_offsets_out (m + 1 entries, starting
+ * at 0), d_sizes_out and d_tiers_out (m entries each).  d_sizes and d_sizes_out may both be
+ * NULL, d_tiers and d_tiers_out likewise; one of a pair without the other is S3IMPH_ERR_INVALID,
+ * as is an order entry >= m.  The outputs go straight into s3imph_aggregate_plan[_tiers]_device.
+ * Synchronous on `stream`. */
+int s3imph_gather_objects_device(s3imph_ctx *ctx, const uint8_t *d_keys, const uint64_t *d_key_offsets,
+                                 const uint64_t *d_sizes, const uint8_t *d_tiers, uint64_t m,
+                                 const uint32_t *d_order, uint8_t *d_keys_out, uint64_t keys_cap,
+                                 uint64_t *d_offsets_out, uint64_t *d_sizes_out, uint8_t *d_tiers_out, void *stream);
+
+/* The same order from host memory (H2D, sort, D2H; aggregator.go:44-76, types.go:160-164):
+ * *order is allocated by the library (m entries; release with s3imph_free), NULL for m == 0,
+ * which touches no device. */
+int s3imph_sort_objects_host(int device, const uint8_t *keys, const uint64_t *key_offsets, uint64_t m,
+                             uint32_t **order, s3imph_sort_info *info, char *err, size_t errlen);
+
+/* s3imph_index_from_objects_host for a listing in any order (aggregator.go:44-76,
+ * types.go:160-164): H2D, sort, gather, the unsorted copy freed, then exactly the row path of
+ * s3imph_index_from_objects_host — s3imph_index_from_objects_tiers_host's when tiers is given
+ * (NULL: no tier files).  The directory is the one those write for the same listing sorted
+ * stably beforehand.  A missing out_dir is S3IMPH_ERR_IO before the device is selected; the
+ * out-of-memory retry of the host builds applies; failures of the sort are worded "sort: ...". */
+int s3imph_index_from_unsorted_objects_host(int device, const uint8_t *keys, const uint64_t *key_offsets,
+                                            const uint64_t *sizes, const uint8_t *tiers, uint64_t m,
+                                            uint32_t max_depth, const char *out_dir, char *err, size_t errlen);
+
+/* ------------------------------------------------------------------------
  * 6. Deterministic synthetic prefix sets (bench/test support, not on the path).
  *    kind: 0 = s3-like, lengths uniform in [max(10, avg/2), 3avg/2],
  *              distinct and byte-sorted;

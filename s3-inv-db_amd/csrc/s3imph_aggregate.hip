@@ -811,10 +811,45 @@ struct DevRows {
   uint64_t present_mask = 0;
 };
 
-// H2D of the listing, plan, fill (with `tiers`: the tier forms and the tier columns too); the
-// listing's device copy is freed before returning.
+// The listing's device copy put into byte order (s3imph_sort.hip): sort, gather out of place,
+// free the unsorted copy.  A listing found sorted stays as it is.
+int sort_listing(s3imph_ctx* c, DevGuard& g, uint8_t*& d_keys, uint64_t*& d_koff, uint64_t*& d_sizes,
+                 uint8_t*& d_tiers, uint64_t m, hipStream_t s, std::string* msg) {
+  try {
+    uint32_t* d_order = nullptr;
+    g.make(d_order, m);
+    s3imph_sort_info si;
+    int rc = sort_objects(c, d_keys, d_koff, m, d_order, &si, s, msg);
+    if (rc == S3IMPH_OK && si.first_unsorted != UINT64_MAX) {
+      uint8_t *keys2 = nullptr, *tiers2 = nullptr;
+      uint64_t *koff2 = nullptr, *sizes2 = nullptr;
+      const uint64_t cap = (si.key_bytes + 7) & ~7ull;
+      g.make(keys2, cap + 16);
+      g.make(koff2, m + 1);
+      if (d_sizes) g.make(sizes2, m);
+      if (d_tiers) g.make(tiers2, m);
+      rc = gather_objects(c, d_keys, d_koff, d_sizes, d_tiers, m, d_order, keys2, cap, koff2, sizes2, tiers2, s, msg);
+      g.drop(d_keys);
+      g.drop(d_koff);
+      g.drop(d_sizes);
+      g.drop(d_tiers);
+      d_keys = keys2;
+      d_koff = koff2;
+      d_sizes = sizes2;
+      d_tiers = tiers2;
+    }
+    g.drop(d_order);
+    return rc;
+  } catch (const Fail& f) {
+    throw Fail{f.code, "sort: " + f.msg};
+  }
+}
+
+// H2D of the listing, plan, fill (with `tiers`: the tier forms and the tier columns too; with
+// `unsorted`: the sort and the gather first); the listing's device copy is freed before returning.
 int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes,
-                   uint64_t m, uint32_t max_depth, DevRows* out, std::string* msg, const uint8_t* tiers = nullptr) {
+                   uint64_t m, uint32_t max_depth, DevRows* out, std::string* msg, const uint8_t* tiers = nullptr,
+                   bool unsorted = false) {
   hipStream_t s = c->own_stream;
   uint8_t *d_keys = nullptr, *d_tiers = nullptr;
   uint64_t *d_koff = nullptr, *d_sizes = nullptr;
@@ -831,6 +866,10 @@ int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64
     if (tiers) {
       g.make(d_tiers, m);
       HIPCHECK(hipMemcpy(d_tiers, tiers, m, hipMemcpyHostToDevice));
+    }
+    if (unsorted) {
+      const int rc0 = sort_listing(c, g, d_keys, d_koff, d_sizes, d_tiers, m, s, msg);
+      if (rc0 != S3IMPH_OK) return rc0;
     }
   }
   s3imph_agg_info info;
@@ -1077,10 +1116,13 @@ int s3imph_aggregate_tiers_host(int device, const uint8_t* keys, const uint64_t*
                              depth, object_count, total_bytes, tier_count, tier_bytes, present_mask, n, err, errlen);
 }
 
-// s3imph_index_from_objects_host, and with `tiers` s3imph_index_from_objects_tiers_host.
-static int index_from_objects_impl(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
-                                   const uint8_t* tiers, uint64_t m, uint32_t max_depth, const char* out_dir,
-                                   char* err, size_t errlen) {
+}  // extern "C"
+
+// s3imph_index_from_objects_host, with `tiers` s3imph_index_from_objects_tiers_host, and with
+// `unsorted` s3imph_index_from_unsorted_objects_host (s3imph_sort.hip).
+int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
+                               const uint8_t* tiers, uint64_t m, uint32_t max_depth, const char* out_dir,
+                               bool unsorted, char* err, size_t errlen) {
   if (!out_dir || !listing_given(keys, key_offsets, m)) return S3IMPH_ERR_INVALID;
   const std::string dir = out_dir;
   if (!is_dir(dir)) {
@@ -1108,7 +1150,7 @@ static int index_from_objects_impl(int device, const uint8_t* keys, const uint64
       const int rc = retry_on_nomem(c, s, &msg, [&]() -> int {
         DevGuard g;
         DevRows r;
-        int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers);
+        int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers, unsorted);
         if (rc2 != S3IMPH_OK) return rc2;
         n = r.n;
         if (tiers) {  // the columns of the present tiers leave HBM before the build needs the room
@@ -1189,7 +1231,8 @@ static int index_from_objects_impl(int device, const uint8_t* keys, const uint64
     if (rc != S3IMPH_OK) set_err(err, errlen, msg);
     return rc;
   } catch (const Fail& f) {
-    set_err(err, errlen, "aggregate: " + f.msg);
+    // a failure inside the sort stage comes worded "sort: ..." (rows_from_host)
+    set_err(err, errlen, f.msg.compare(0, 6, "sort: ") == 0 ? f.msg : "aggregate: " + f.msg);
     return f.code;
   } catch (const std::bad_alloc&) {
     set_err(err, errlen, "aggregate: out of host memory");
@@ -1197,10 +1240,12 @@ static int index_from_objects_impl(int device, const uint8_t* keys, const uint64
   }
 }
 
+extern "C" {
+
 int s3imph_index_from_objects_host(int device, const uint8_t* keys, const uint64_t* key_offsets,
                                    const uint64_t* sizes, uint64_t m, uint32_t max_depth, const char* out_dir,
                                    char* err, size_t errlen) {
-  return index_from_objects_impl(device, keys, key_offsets, sizes, nullptr, m, max_depth, out_dir, err, errlen);
+  return index_from_objects(device, keys, key_offsets, sizes, nullptr, m, max_depth, out_dir, false, err, errlen);
 }
 
 int s3imph_index_from_objects_tiers_host(int device, const uint8_t* keys, const uint64_t* key_offsets,
@@ -1208,8 +1253,8 @@ int s3imph_index_from_objects_tiers_host(int device, const uint8_t* keys, const 
                                          const char* out_dir, char* err, size_t errlen) {
   static const uint8_t kNone = 0;
   if (m && !tiers) return S3IMPH_ERR_INVALID;
-  return index_from_objects_impl(device, keys, key_offsets, sizes, tiers ? tiers : &kNone, m, max_depth, out_dir, err,
-                                 errlen);
+  return index_from_objects(device, keys, key_offsets, sizes, tiers ? tiers : &kNone, m, max_depth, out_dir, false,
+                            err, errlen);
 }
 
 }  // extern "C"

@@ -2507,14 +2507,16 @@ bool reclaim_cached(s3imph_ctx* keep, const void* keep_set) {
       free_workspace(c);
       fin_scratch_free(c);
       agg_scratch_free(c);
+      sort_scratch_free(c);
       c->have_build = false;
       c->rank_valid = false;
       any = true;
     }
   }
-  if (keep && (keep->fin || keep->agg)) {
+  if (keep && (keep->fin || keep->agg || keep->srt)) {
     fin_scratch_free(keep);
     agg_scratch_free(keep);
+    sort_scratch_free(keep);
     any = true;
   }
   if (keep) (void)hipSetDevice(keep->device);
@@ -3096,6 +3098,7 @@ int s3imph_ctx_destroy(s3imph_ctx* c) {
   free_workspace(c);
   fin_scratch_free(c);
   agg_scratch_free(c);
+  sort_scratch_free(c);
   if (c->d.xo) (void)hipStreamSynchronize(c->d.xo);
   delete c->d.xcomm;
   c->d.xcomm = nullptr;
@@ -3506,6 +3509,7 @@ int s3imph_release_workspaces(void) {
     free_workspace(c);
     fin_scratch_free(c);
     agg_scratch_free(c);
+    sort_scratch_free(c);
     c->have_build = false;
     c->rank_valid = false;
   }

@@ -201,12 +201,14 @@ using s3imph::Stager;
 namespace s3imph {
 struct FinScratch;  // s3imph_finalize.hip
 struct AggScratch;  // s3imph_aggregate.hip
+struct SortScratch;  // s3imph_sort.hip
 }
 
 struct s3imph_ctx {
   int device = 0;
   s3imph::FinScratch* fin = nullptr;  // finalize-pass scratch (s3imph_finalize.hip), lazily made
   s3imph::AggScratch* agg = nullptr;  // aggregation scratch and the last plan (s3imph_aggregate.hip), lazily made
+  s3imph::SortScratch* srt = nullptr;  // listing sort / gather scratch (s3imph_sort.hip), lazily made
   uint32_t* mid = nullptr;            // k_mid_levels scratch (kMidScratchU32, or the 256-workgroup form's), lazily made
   uint64_t mid_cap = 0;               // ... its u32 words
   Rec* split = nullptr;               // k_tile_split scratch, made for sets big enough for 2^15+ tiles
@@ -364,6 +366,21 @@ int aggregate_plan(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, con
 int aggregate_fill(s3imph_ctx* c, uint8_t* blob, uint64_t blob_cap, uint64_t* offsets, uint32_t* depth,
                    uint64_t* ocnt, uint64_t* tbytes, uint64_t n_cap, hipStream_t s, std::string* msg);
 void agg_scratch_free(s3imph_ctx* c);
+// Listing to directory (s3imph_aggregate.hip): the row path behind s3imph_index_from_objects[_tiers]_host
+// (tiers nullable); with `unsorted` the listing's device copy is sorted and gathered first
+// (s3imph_index_from_unsorted_objects_host).
+int index_from_objects(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
+                       const uint8_t* tiers, uint64_t m, uint32_t max_depth, const char* out_dir, bool unsorted,
+                       char* err, size_t errlen);
+// Listing sort (s3imph_sort.hip): the byte order of m object keys in HBM (order[j] = input index
+// of the j-th key, equal keys in input order; fills *info) and the out-of-place gather of the
+// listing into an order; both wait for the stream.
+int sort_objects(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, uint64_t m, uint32_t* order,
+                 s3imph_sort_info* info, hipStream_t s, std::string* msg);
+int gather_objects(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes,
+                   const uint8_t* tiers, uint64_t m, const uint32_t* order, uint8_t* keys_out, uint64_t keys_cap,
+                   uint64_t* off_out, uint64_t* sizes_out, uint8_t* tiers_out, hipStream_t s, std::string* msg);
+void sort_scratch_free(s3imph_ctx* c);
 // A context (s3imph_ctx_create) whose multi-GPU collectives go through `comm` (owned).
 s3imph_ctx* make_dist_ctx(int device, Comm* comm, int rank, int nranks, std::string* msg);
 

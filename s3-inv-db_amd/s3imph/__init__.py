@@ -14,7 +14,9 @@ plus the device-resident API that bench.py times (``DeviceBuilder``), the
 multi-GPU rank API (``DistBuilder``), the batched lookup (``MPHF``), the reader,
 ``Index`` (indexread.Index: Open / Lookup / Stats / Descendants* over a batch), and the front
 of the pipeline: ``aggregate`` (extsort.Aggregator + SortPrefixRows: object listing -> prefix
-rows) and ``build_index_from_objects`` (object listing -> index directory).  With one tier id
+rows) and ``build_index_from_objects`` (object listing -> index directory), both for a
+byte-sorted listing; ``sort_objects`` and ``build_index_from_unsorted_objects`` take one in any
+order (the stable byte-order sort and the gather run on the GPU too).  With one tier id
 per object (``TIERS``, ``tier_from_s3``) both also carry the per-storage-class statistics that
 ``Index.tier_breakdown*`` answer from.
 
@@ -81,6 +83,8 @@ EXPORTS = (
     "s3imph_aggregate_plan_tiers_device", "s3imph_aggregate_fill_tiers_device", "s3imph_aggregate_tiers_host",
     "s3imph_index_from_objects_tiers_host", "s3imph_write_tier_files",
     "s3imph_index_attach_tiers", "s3imph_index_tier_count", "s3imph_index_tier_ids", "s3imph_index_tiers_device",
+    "s3imph_sort_objects_device", "s3imph_gather_objects_device", "s3imph_sort_objects_host",
+    "s3imph_index_from_unsorted_objects_host",
 )
 NUM_TIERS = 12  # S3IMPH_NUM_TIERS
 
@@ -145,6 +149,17 @@ class AggInfo(ctypes.Structure):
 class AggTierInfo(ctypes.Structure):
     """s3imph_agg_tier_info: what a plan with tiers found (include/s3imph.h, section 5e)."""
     _fields_ = [("present_mask", ctypes.c_uint64), ("first_bad_tier", ctypes.c_uint64)]
+
+
+class SortInfo(ctypes.Structure):
+    """s3imph_sort_info: what a listing sort found (include/s3imph.h, section 5f)."""
+    _fields_ = [
+        ("n_objects", ctypes.c_uint64), ("key_bytes", ctypes.c_uint64), ("first_unsorted", ctypes.c_uint64),
+        ("n_equal", ctypes.c_uint64), ("rounds", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
 
 
 # s3imph_node: what Index.nodes returns, one record per queried position
@@ -234,6 +249,10 @@ def _load():
         "s3imph_index_tier_count": (u64, [vp]),
         "s3imph_index_tier_ids": (u64, [vp, vp, u64]),
         "s3imph_index_tiers_device": (i32, [vp, vp, u64, vp, vp, vp]),
+        "s3imph_sort_objects_device": (i32, [vp, vp, vp, u64, vp, P(SortInfo), vp]),
+        "s3imph_gather_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]),
+        "s3imph_sort_objects_host": (i32, [i32, vp, vp, u64, P(vp), P(SortInfo), cp, sz]),
+        "s3imph_index_from_unsorted_objects_host": (i32, [i32, vp, vp, vp, vp, u64, ctypes.c_uint32, cp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -631,6 +650,47 @@ class DeviceBuilder:
             raise MPHFError(rc, self.last_error() or f"aggregate: {status_string(rc)}")
         return {"tier_count": tc, "tier_bytes": tb, "n": n, "present_mask": info.get("present_mask", 0)}
 
+    def sort_objects(self, d_keys, d_key_offsets, m: int, stream=None):
+        """s3imph_sort_objects_device: the byte order of an object listing in HBM, in any order
+        (what SortPrefixRows' comparison gives, types.go:160-164; stable).  Returns (order, info):
+        order an int32 tensor holding the u32 bits, order[j] = the input index of the j-th key in
+        sorted order; info s3imph_sort_info as a dict (n_objects, key_bytes, first_unsorted,
+        n_equal, rounds).  A refusal raises MPHFError with that dict as ``.info``."""
+        import torch
+        dev = f"cuda:{self.device}" if d_key_offsets is None else d_key_offsets.device
+        order = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        info = SortInfo()
+        rc = LIB.s3imph_sort_objects_device(self._h, _dev_ptr(d_keys), _dev_ptr(d_key_offsets), m, _dev_ptr(order),
+                                            ctypes.byref(info), _stream_ptr(stream))
+        self.last_sort = info.as_dict()
+        if rc != OK:
+            e = MPHFError(rc, self.last_error() or f"sort: {status_string(rc)}")
+            e.info = self.last_sort
+            raise e
+        return order[:m], self.last_sort
+
+    def gather_objects(self, d_keys, d_key_offsets, m: int, d_order, d_sizes=None, d_tiers=None,
+                       keys_cap: int | None = None, stream=None) -> dict:
+        """s3imph_gather_objects_device: the listing put into the order d_order, out of place, as
+        torch tensors: keys (uint8, padded with zeros to 8 bytes), offsets (int64, m + 1, starting
+        at 0), sizes (int64 holding the u64 bits, or None without d_sizes), tiers (uint8, or None
+        without d_tiers), key_bytes.  keys_cap defaults to what the listing needs."""
+        import torch
+        dev = f"cuda:{self.device}" if d_key_offsets is None else d_key_offsets.device
+        nbytes = int(d_key_offsets[m] - d_key_offsets[0]) if m else 0
+        keys_cap = (nbytes + 7) // 8 * 8 if keys_cap is None else keys_cap
+        keys = torch.empty(max(keys_cap, 8), dtype=torch.uint8, device=dev)
+        offs = torch.empty(m + 1, dtype=torch.int64, device=dev)
+        sizes = None if d_sizes is None else torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+        tiers = None if d_tiers is None else torch.empty(max(m, 1), dtype=torch.uint8, device=dev)
+        rc = LIB.s3imph_gather_objects_device(self._h, _dev_ptr(d_keys), _dev_ptr(d_key_offsets), _dev_ptr(d_sizes),
+                                              _dev_ptr(d_tiers), m, _dev_ptr(d_order), _dev_ptr(keys), keys_cap,
+                                              _dev_ptr(offs), _dev_ptr(sizes), _dev_ptr(tiers), _stream_ptr(stream))
+        if rc != OK:
+            raise MPHFError(rc, self.last_error() or f"sort: {status_string(rc)}")
+        return {"keys": keys[: (nbytes + 7) // 8 * 8], "offsets": offs, "sizes": None if sizes is None else sizes[:m],
+                "tiers": None if tiers is None else tiers[:m], "key_bytes": nbytes}
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             LIB.s3imph_ctx_destroy(self._h)
@@ -725,6 +785,39 @@ def build_index_from_objects(keys_blob: np.ndarray, key_offsets: np.ndarray, siz
         tr = _tier_ids(tiers, m)
         _check(LIB.s3imph_index_from_objects_tiers_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), _np_ptr(tr),
                                                         m, max_depth, os.fsencode(out_dir), err, 1024), err)
+
+
+def sort_objects(keys_blob: np.ndarray, key_offsets: np.ndarray, device: int = 0):
+    """s3imph_sort_objects_host: the byte order of an object listing in any order (unsigned bytes,
+    a proper prefix first, equal keys in input order: SortPrefixRows' comparison, types.go:160-164)
+    -> (order u32[m], info dict); order[j] is the input index of the j-th key in sorted order."""
+    blob, offs, _, m = _listing(keys_blob, key_offsets, None)
+    p = ctypes.c_void_p()
+    info = SortInfo()
+    err = ctypes.create_string_buffer(1024)
+    rc = LIB.s3imph_sort_objects_host(device, _np_ptr(blob), _np_ptr(offs), m, ctypes.byref(p), ctypes.byref(info),
+                                      err, 1024)
+    try:
+        _check(rc, err)
+        order = np.zeros(m, np.uint32)
+        if m and p.value:
+            ctypes.memmove(order.ctypes.data, p.value, order.nbytes)
+        return order, info.as_dict()
+    finally:
+        if p.value:
+            LIB.s3imph_free(p)
+
+
+def build_index_from_unsorted_objects(keys_blob: np.ndarray, key_offsets: np.ndarray, sizes: np.ndarray | None,
+                                      out_dir: str, tiers=None, max_depth: int = 0, device: int = 0) -> None:
+    """build_index_from_objects for a listing in any order (s3imph_index_from_unsorted_objects_host):
+    the listing is sorted (stably) and gathered on the GPU, then takes the same path; the directory
+    is the one build_index_from_objects writes for the listing sorted beforehand."""
+    blob, offs, sz, m = _listing(keys_blob, key_offsets, sizes)
+    tr = None if tiers is None else _tier_ids(tiers, m)
+    err = ctypes.create_string_buffer(1024)
+    _check(LIB.s3imph_index_from_unsorted_objects_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), _np_ptr(tr),
+                                                       m, max_depth, os.fsencode(out_dir), err, 1024), err)
 
 
 def write_manifest(out_dir: str, node_count: int, max_depth: int) -> None:
