@@ -28,26 +28,17 @@
 // one scan turns the 24 columns of tile sums into wrapping prefixes, and the emit — one lane per
 // row, adjacent lanes adjacent rows, 24 coalesced column writes — takes the whole tiles of [i, e)
 // from the table and walks the two partial tiles (fewer than 2 kTG elements, whatever e - i is).
-#include <rocprim/device/device_scan.hpp>
-
 #include <sys/stat.h>
 
 #include <cstdlib>
 #include <cstring>
 
 #include "s3imph_ctx.h"
-#include "s3imph_device.h"
+#include "s3imph_keys.h"
+#include "s3imph_prim.h"
 #include "s3imph_tiers.h"
 
 namespace s3imph {
-
-s3imph_ctx* default_ctx(int device, std::string* msg);
-int write_finalize_files(const std::string& dir, const uint32_t* depth, const uint64_t* subtree_end,
-                         const uint32_t* max_depth_sub, const uint64_t* depth_offsets, uint64_t n_offsets,
-                         const uint64_t* depth_positions, uint64_t n, std::string* msg);
-int write_stats_files(const std::string& dir, const uint64_t* object_count, const uint64_t* total_bytes, uint64_t n,
-                      std::string* msg);
-int write_manifest(const std::string& dir, uint64_t node_count, uint32_t max_depth, std::string* msg);
 
 namespace {
 
@@ -66,39 +57,6 @@ struct AggTop {
   unsigned long long first_unsorted, first_deep;
   unsigned maxd, pad;
 };
-
-// 8 key bytes from blob address a (any alignment); the blob is readable up to end8 =
-// round_up(offsets[m], 8).  (As in s3imph_finalize.hip.)
-__device__ __forceinline__ uint64_t load8(const uint8_t* blob, uint64_t a, uint64_t end8) {
-  const uint64_t al = a & ~7ull;
-  const uint64_t* w = reinterpret_cast<const uint64_t*>(blob + al);
-  const uint64_t lo = w[0];
-  const uint64_t hi = (a & 7) && al + 8 < end8 ? w[1] : 0;
-  return (a & 7) ? funnel_bytes(lo, hi, (unsigned)(a & 7)) : lo;
-}
-
-// bit 8j+7 set iff byte j of the first `valid` (1..8) bytes of x is '/'
-__device__ __forceinline__ uint64_t slash_bits(uint64_t x, uint64_t valid) {
-  constexpr uint64_t k7f = 0x7f7f7f7f7f7f7f7full;
-  x ^= 0x2f2f2f2f2f2f2f2full;
-  const uint64_t t = (x & k7f) + k7f;
-  uint64_t z = ~(t | x | k7f);
-  if (valid < 8) z &= (1ull << (8 * valid)) - 1;
-  return z;
-}
-
-// First index in [lo, hi) with U[index] > u, or hi.
-__device__ __forceinline__ uint64_t first_above(const uint64_t* __restrict__ U, uint64_t lo, uint64_t hi,
-                                                uint64_t u) {
-  uint64_t len = hi - lo;
-  while (len) {
-    const uint64_t h = len >> 1;
-    const bool right = U[lo + h] <= u;
-    lo = right ? lo + h + 1 : lo;
-    len = right ? len - h - 1 : h;
-  }
-  return lo;
-}
 
 // Key pass: per key i its '/' count s and the '/' count c inside the common prefix with key
 // i - 1, found in one walk over the key's words against its predecessor's; the sortedness
@@ -208,15 +166,12 @@ __global__ __launch_bounds__(kAS) void k_agg_super(const uint32_t* __restrict__ 
 }
 
 // The emit kernels cut their output into chunks of kAT units (rows, or 8-byte words of the
-// blob) and need the owner (key, or row) of each chunk's first unit: an upper-bound search in a
-// scan U (entries `entries`) per chunk.  Done here with one lane per chunk, so the searches'
-// dependent loads overlap across chunks instead of standing at the head of every workgroup.
-// out[t] = last index with U[index] <= max(t * step, first_min).
+// blob): the owner (key, or row) of each chunk's first unit, one lane per chunk (chunk_owner).
 __global__ __launch_bounds__(kAT) void k_agg_bounds(const uint64_t* __restrict__ U, uint64_t entries, uint64_t step,
                                                     uint64_t first_min, uint64_t nchunks,
                                                     uint64_t* __restrict__ out) {
   const uint64_t t = (uint64_t)blockIdx.x * kAT + threadIdx.x;
-  if (t < nchunks) out[t] = first_above(U, 0, entries, max(t * step, first_min)) - 1;
+  if (t < nchunks) out[t] = chunk_owner(U, entries, step, first_min, t);
 }
 
 // Emit, by output row: row r > 0 belongs to the key i with rowbase[i] <= r < rowbase[i+1]
@@ -325,48 +280,15 @@ __global__ __launch_bounds__(kAT) void k_agg_rows(const uint8_t* __restrict__ bl
   }
 }
 
-// Emit, by output bytes: each lane assembles one 8-byte word of prefix_blob.  The row of a byte
-// is the last one that starts at or before it (upper-bound search in the row offsets inside
-// the workgroup's rows, k_agg_bounds); its source is the row's key at the same distance from the
-// key's start.  A word takes one unaligned 8-byte read of the key blob per row it overlaps
-// (rows average a few words, so mostly one or two).  Bytes past blob_bytes in the last word
-// are zeros.
+// Emit, by output bytes (emit_word): each lane assembles one 8-byte word of prefix_blob; the
+// source of row r is its key, rowsrc[r], at the same distance from the key's start (rows average
+// a few words, so a word mostly takes one or two reads).
 __global__ __launch_bounds__(kAT) void k_agg_bytes(const uint8_t* __restrict__ blob, uint64_t key_end8,
                                                    const uint64_t* __restrict__ offsets,
                                                    const uint64_t* __restrict__ rowsrc,
                                                    const uint64_t* __restrict__ bounds, uint64_t n,
                                                    uint64_t blob_bytes, uint8_t* __restrict__ out) {
-  const uint64_t wbase = (uint64_t)blockIdx.x * kAT;
-  const uint64_t nw = (blob_bytes + 7) / 8;
-  if (wbase >= nw) return;
-  const uint64_t wend = min(nw, wbase + kAT);
-  // offsets has n + 1 entries, offsets[0] = 0, offsets[n] = blob_bytes
-  const uint64_t r_lo = bounds[blockIdx.x];
-  const uint64_t r_hi = blockIdx.x + 1 < gridDim.x ? bounds[blockIdx.x + 1] : n - 1;
-  const uint64_t wi = wbase + threadIdx.x;
-  if (wi >= wend) return;
-  const uint64_t a = 8 * wi, aend = min(a + 8, blob_bytes);
-  uint64_t r = first_above(offsets, r_lo + 1, r_hi + 1, a) - 1;
-  uint64_t o0 = offsets[r], o1 = offsets[r + 1];
-  uint64_t v = 0;
-  for (uint64_t p = a; p < aend;) {
-    while (o1 <= p) {  // offsets[n] = blob_bytes > p ends it
-      ++r;
-      o0 = o1;
-      o1 = offsets[r + 1];
-    }
-    const uint64_t cnt = min(o1, aend) - p;  // bytes of row r in this word, 1..8
-    // the read may run past the row's key, never past the blob's readable end
-    const uint64_t x = load8(blob, rowsrc[r] + (p - o0), key_end8);
-    v |= (cnt >= 8 ? x : x & ((1ull << (8 * cnt)) - 1)) << (8 * (p - a));
-    p += cnt;
-  }
-  if (((uintptr_t)out & 7) == 0) {
-    *reinterpret_cast<uint64_t*>(out + a) = v;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) out[a + j] = (uint8_t)(v >> (8 * j));
-  }
+  emit_word<kAT>(blob, key_end8, offsets, bounds, n, blob_bytes, out, [&](uint64_t r) { return rowsrc[r]; });
 }
 
 // ---- the per-tier columns ----------------------------------------------------------------
@@ -489,8 +411,7 @@ struct AggScratch {
   uint64_t rows_cap = 0;
   uint64_t* bounds = nullptr;  // the emit chunks' first owners (k_agg_bounds)
   uint64_t bounds_cap = 0;
-  void* tmp = nullptr;
-  size_t tmp_cap = 0;
+  PrimTmp tmp;
   // the tier columns: the prefix table (2 kNT columns of tiles + 1 entries), what the tile pass
   // reports, each row's key range [i, e) (kept by the fill of a plan with tiers)
   uint64_t* ttab = nullptr;
@@ -518,12 +439,11 @@ struct AggScratch {
     dfree(top);
     dfree(rowsrc);
     dfree(bounds);
-    dfree(tmp);
+    tmp.release();
     dfree(ttab);
     dfree(ttop);
     dfree(rowrange);
     cap = rows_cap = bounds_cap = ttab_cap = range_cap = 0;
-    tmp_cap = 0;
     have_plan = false;
   }
 };
@@ -535,22 +455,6 @@ void agg_scratch_free(s3imph_ctx* c) {
     c->agg = nullptr;
   }
 }
-
-namespace {
-
-void scan_u64(AggScratch& a, uint64_t* v, uint64_t count, uint64_t init, hipStream_t s) {
-  size_t need = 0;
-  HIPCHECK(rocprim::exclusive_scan(nullptr, need, v, v, init, count, rocprim::plus<uint64_t>(), s));
-  if (need > a.tmp_cap) {
-    dfree(a.tmp);
-    a.tmp_cap = 0;
-    HIPCHECK(hipMalloc(&a.tmp, need));
-    a.tmp_cap = need;
-  }
-  HIPCHECK(rocprim::exclusive_scan(a.tmp, need, v, v, init, count, rocprim::plus<uint64_t>(), s));
-}
-
-}  // namespace
 
 // Plan: the key pass and the scans for m keys in HBM; fills *info, keeps the plan in the
 // context.  Waits for the stream.
@@ -591,14 +495,14 @@ int aggregate_plan(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, con
   k_agg_keys<<<(unsigned)nb, kAB, 0, s>>>(keys, koff, m, cap, a.c, a.rowbase, a.keybytes, a.bmin, a.top);
   k_agg_super<<<(unsigned)nsb, kAS, 0, s>>>(a.bmin, nb, a.smin);
   HIPCHECK(hipGetLastError());
-  scan_u64(a, a.rowbase, m + 1, 1, s);  // + 1: the root row
-  scan_u64(a, a.keybytes, m + 1, 0, s);
+  scan_u64(a.tmp, a.rowbase, m + 1, 1, s);  // + 1: the root row
+  scan_u64(a.tmp, a.keybytes, m + 1, 0, s);
   a.sized = sizes != nullptr;
   uint64_t tot[4] = {0, 0, 0, 0};  // rows, row bytes, size sum, end of the key blob
   if (sizes) {
     HIPCHECK(hipMemcpyAsync(a.Z, sizes, m * 8, hipMemcpyDeviceToDevice, s));
     HIPCHECK(hipMemsetAsync(a.Z + m, 0, 8, s));
-    scan_u64(a, a.Z, m + 1, 0, s);
+    scan_u64(a.tmp, a.Z, m + 1, 0, s);
     HIPCHECK(hipMemcpyAsync(&tot[2], a.Z + m, 8, hipMemcpyDeviceToHost, s));
   }
   HIPCHECK(hipMemcpyAsync(&top, a.top, sizeof top, hipMemcpyDeviceToHost, s));
@@ -659,26 +563,14 @@ int aggregate_fill(s3imph_ctx* c, uint8_t* blob, uint64_t blob_cap, uint64_t* of
     a.ranges_kept = a.tiered;
     return S3IMPH_OK;
   }
-  if (a.n > a.rows_cap) {
-    a.rows_cap = 0;
-    dalloc(a.rowsrc, a.n);
-    a.rows_cap = a.n;
-  }
+  grow(a.rowsrc, a.rows_cap, a.n);
   const uint64_t nb = (a.m + kAB - 1) / kAB, nsb = (nb + kAS - 1) / kAS;
   const uint64_t nw = (a.blob_bytes + 7) / 8;
   const uint64_t rchunks = (a.n + kAT - 1) / kAT, wchunks = (nw + kAT - 1) / kAT;
-  if (std::max(rchunks, wchunks) > a.bounds_cap) {
-    a.bounds_cap = 0;
-    dalloc(a.bounds, std::max(rchunks, wchunks));
-    a.bounds_cap = std::max(rchunks, wchunks);
-  }
+  grow(a.bounds, a.bounds_cap, std::max(rchunks, wchunks));
   k_agg_bounds<<<(unsigned)((rchunks + kAT - 1) / kAT), kAT, 0, s>>>(a.rowbase, a.m + 1, kAT, 1, rchunks, a.bounds);
   if (a.tiered) {
-    if (a.n > a.range_cap) {
-      a.range_cap = 0;
-      dalloc(a.rowrange, 2 * a.n);
-      a.range_cap = a.n;
-    }
+    grow(a.rowrange, a.range_cap, 2 * a.n);
     k_agg_rows<true><<<(unsigned)rchunks, kAT, 0, s>>>(a.keys, a.koff, a.m, a.depth_cap, a.c, a.rowbase, a.keybytes,
                                                        a.bounds, a.sized ? a.Z : nullptr, a.bmin, a.smin, nb, nsb, a.n,
                                                        a.blob_bytes, offsets, depth, ocnt, tbytes, a.rowsrc,
@@ -716,11 +608,7 @@ int aggregate_plan_tiers(s3imph_ctx* c, const uint8_t* keys, const uint64_t* kof
   a.present_mask = 0;
   if (m) {
     const uint64_t tiles = (m + kTG - 1) / kTG, ntp = tiles + 1;
-    if (2 * kNT * ntp > a.ttab_cap) {
-      a.ttab_cap = 0;
-      dalloc(a.ttab, 2 * kNT * ntp);
-      a.ttab_cap = 2 * kNT * ntp;
-    }
+    grow(a.ttab, a.ttab_cap, 2 * kNT * ntp);
     if (!a.ttop) dalloc(a.ttop, 1);
     TierTop top;
     std::memset(&top, 0, sizeof top);
@@ -728,7 +616,7 @@ int aggregate_plan_tiers(s3imph_ctx* c, const uint8_t* keys, const uint64_t* kof
     HIPCHECK(hipMemcpyAsync(a.ttop, &top, sizeof top, hipMemcpyHostToDevice, s));
     k_agg_tier_tiles<<<(unsigned)((tiles + kTW - 1) / kTW), kTG * kTW, 0, s>>>(tiers, sizes, m, tiles, a.ttab, a.ttop);
     HIPCHECK(hipGetLastError());
-    scan_u64(a, a.ttab, 2 * kNT * ntp, 0, s);
+    scan_u64(a.tmp, a.ttab, 2 * kNT * ntp, 0, s);
     k_agg_tier_totals<<<1, 64, 0, s>>>(a.ttab, ntp, a.ttop);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(&top, a.ttop, sizeof top, hipMemcpyDeviceToHost, s));
@@ -777,28 +665,20 @@ int aggregate_fill_tiers(s3imph_ctx* c, uint64_t* tcount, uint64_t* tbytes, uint
   return S3IMPH_OK;
 }
 
-namespace {
+bool listing_given(const uint8_t* keys, const uint64_t* koff, uint64_t m) {
+  return m == 0 || (koff && (keys || koff[m] == koff[0]));
+}
 
-struct DevGuard {
-  std::vector<void*> p;
-  template <typename T>
-  void make(T*& q, uint64_t count) {
-    dalloc(q, count);
-    p.push_back(q);
-  }
-  void drop(void* q) {
-    if (!q) return;
-    for (void*& x : p)
-      if (x == q) {
-        (void)hipFree(x);
-        x = nullptr;
-      }
-  }
-  ~DevGuard() {
-    for (void* q : p)
-      if (q) (void)hipFree(q);
-  }
-};
+void upload_keys(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t* koff, uint64_t m,
+                    uint8_t*& d_keys, uint64_t*& d_koff) {
+  const uint64_t b0 = koff[0], nbytes = koff[m] - b0;
+  g.make(d_keys, ((nbytes + 7) & ~7ull) + 16);
+  g.make(d_koff, m + 1);
+  if (nbytes) HIPCHECK(hipMemcpy(d_keys, keys + b0, nbytes, hipMemcpyHostToDevice));
+  staged_copy(c, true, d_koff, koff, (m + 1) * 8, b0);
+}
+
+namespace {
 
 // The prefix rows of a host listing, left in HBM (owned by g).
 struct DevRows {
@@ -854,11 +734,7 @@ int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64
   uint8_t *d_keys = nullptr, *d_tiers = nullptr;
   uint64_t *d_koff = nullptr, *d_sizes = nullptr;
   if (m) {
-    const uint64_t b0 = koff[0], nbytes = koff[m] - b0;
-    g.make(d_keys, ((nbytes + 7) & ~7ull) + 16);
-    g.make(d_koff, m + 1);
-    if (nbytes) HIPCHECK(hipMemcpy(d_keys, keys + b0, nbytes, hipMemcpyHostToDevice));
-    staged_copy(c, true, d_koff, koff, (m + 1) * 8, b0);
+    upload_keys(c, g, keys, koff, m, d_keys, d_koff);
     if (sizes) {
       g.make(d_sizes, m);
       staged_copy(c, true, d_sizes, sizes, m * 8);
@@ -905,12 +781,6 @@ T* host_array(uint64_t count) {
   T* p = static_cast<T*>(std::malloc(std::max<uint64_t>(count, 1) * sizeof(T)));
   if (!p) throw std::bad_alloc();
   return p;
-}
-
-// A host listing's pointers: the offsets whenever there are keys, the blob whenever the keys
-// have bytes (a listing of empty keys may come with a NULL blob).
-bool listing_given(const uint8_t* keys, const uint64_t* koff, uint64_t m) {
-  return m == 0 || (koff && (keys || koff[m] == koff[0]));
 }
 
 bool is_dir(const std::string& p) {

@@ -51,6 +51,39 @@ void dalloc(T*& p, uint64_t count) {
   p = static_cast<T*>(v);
 }
 
+// A scratch array of `cap` elements made at least `need` long (its contents are not kept).  The
+// capacity is zeroed before the allocation, so one that throws leaves no capacity over a null
+// pointer for the next call to trust.
+template <typename T>
+void grow(T*& p, uint64_t& cap, uint64_t need) {
+  if (need <= cap) return;
+  cap = 0;
+  dalloc(p, need);
+  cap = need;
+}
+
+// Device arrays of one call, freed when it ends (or earlier, by drop).
+struct DevGuard {
+  std::vector<void*> p;
+  template <typename T>
+  void make(T*& q, uint64_t count) {
+    dalloc(q, count);
+    p.push_back(q);
+  }
+  void drop(void* q) {
+    if (!q) return;
+    for (void*& x : p)
+      if (x == q) {
+        (void)hipFree(x);
+        x = nullptr;
+      }
+  }
+  ~DevGuard() {
+    for (void* q : p)
+      if (q) (void)hipFree(q);
+  }
+};
+
 // Collectives of the multi-GPU build, on device buffers, ordered on stream s.
 struct Comm {
   int rank = 0, nranks = 1;
@@ -301,6 +334,9 @@ struct s3imph_ctx {
 
 namespace s3imph {
 
+// The process's context for `device`, made on first use and kept: what the host-memory entry
+// points run on (s3imph_build.hip).  Null with *msg set when it cannot be made.
+s3imph_ctx* default_ctx(int device, std::string* msg);
 // Builds (s3imph_build.hip).  Both return an s3imph_status and throw Fail on HIP/RCCL errors.
 int build_single(s3imph_ctx* c, const uint8_t* blob, const uint64_t* offsets, const uint64_t* pos, uint64_t n,
                  uint64_t* fp_out, uint64_t* pos_out, hipStream_t s, s3imph_build_info* info, std::string* msg);
@@ -366,6 +402,14 @@ int aggregate_plan(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, con
 int aggregate_fill(s3imph_ctx* c, uint8_t* blob, uint64_t blob_cap, uint64_t* offsets, uint32_t* depth,
                    uint64_t* ocnt, uint64_t* tbytes, uint64_t n_cap, hipStream_t s, std::string* msg);
 void agg_scratch_free(s3imph_ctx* c);
+// Host keys as (blob, offsets) (s3imph_aggregate.hip).  listing_given: a listing's pointers are
+// there — the offsets whenever there are keys, the blob whenever the keys have bytes (a listing of
+// empty keys may come with a NULL blob).  upload_keys (m > 0): the keys on the device, owned by
+// g — the key bytes from koff[0] on, readable 16 bytes past their end rounded up to 8, and the
+// m + 1 offsets less koff[0].
+bool listing_given(const uint8_t* keys, const uint64_t* koff, uint64_t m);
+void upload_keys(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t* koff, uint64_t m,
+                    uint8_t*& d_keys, uint64_t*& d_koff);
 // Listing to directory (s3imph_aggregate.hip): the row path behind s3imph_index_from_objects[_tiers]_host
 // (tiers nullable); with `unsorted` the listing's device copy is sorted and gathered first
 // (s3imph_index_from_unsorted_objects_host).

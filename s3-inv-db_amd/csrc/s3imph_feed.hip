@@ -29,8 +29,6 @@
 
 namespace s3imph {
 
-s3imph_ctx* default_ctx(int device, std::string* msg);
-
 namespace {
 
 constexpr uint64_t kMinChunk = 256ull << 10;  // first chunk of an arena; each next one doubles

@@ -24,40 +24,18 @@
 // run by walking the block hierarchy; the depth index is a stable radix sort of the
 // positions by depth (rocPRIM, bits = bit width of maxDepth) plus a boundary pass.  All
 // integer work, HBM-bound: ΣL·2 + 32 B per key for the pass over the keys.
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "s3imph_ctx.h"
-#include "s3imph_device.h"
+#include "s3imph_keys.h"
+#include "s3imph_prim.h"
 
 namespace s3imph {
-
-int write_finalize_files(const std::string& dir, const uint32_t* depth, const uint64_t* subtree_end,
-                         const uint32_t* max_depth_sub, const uint64_t* depth_offsets, uint64_t n_offsets,
-                         const uint64_t* depth_positions, uint64_t n, std::string* msg);
-s3imph_ctx* default_ctx(int device, std::string* msg);
 
 namespace {
 
 constexpr int kFB = 1024;   // keys per block (one block-minimum of lcp / maximum of depth)
 constexpr int kFS = 1024;   // blocks per superblock
-
-// 8 key bytes from blob address a (any alignment): two aligned words and a byte funnel.
-// The blob is readable up to end8 = round_up(offsets[n], 8).
-__device__ __forceinline__ uint64_t load8(const uint8_t* blob, uint64_t a, uint64_t end8) {
-  const uint64_t al = a & ~7ull;
-  const uint64_t* w = reinterpret_cast<const uint64_t*>(blob + al);
-  const uint64_t lo = w[0];
-  const uint64_t hi = (a & 7) && al + 8 < end8 ? w[1] : 0;
-  return (a & 7) ? funnel_bytes(lo, hi, (unsigned)(a & 7)) : lo;
-}
-
-// exact per-byte zero test: high bit of each byte of the result set iff that byte of x is 0
-__device__ __forceinline__ uint64_t zero_bytes(uint64_t x) {
-  constexpr uint64_t k7f = 0x7f7f7f7f7f7f7f7full;
-  const uint64_t t = (x & k7f) + k7f;
-  return ~(t | x | k7f);
-}
 
 // Pass 1: per key depth ('/' count, or the caller's), lcp with the next key; block
 // minima of lcp (int32; -1 marks the last key) and maxima of depth; the global maxDepth.
@@ -79,9 +57,7 @@ __global__ __launch_bounds__(kFB) void k_fin_keys(const uint8_t* __restrict__ bl
       d = depths_in[i];
     } else {
       for (uint64_t k = 0; k < len; k += 8) {
-        uint64_t z = zero_bytes(load8(blob, b0 + k, end8) ^ 0x2f2f2f2f2f2f2f2full);  // '/' bytes
-        if (len - k < 8) z &= (1ull << (8 * (len - k))) - 1;
-        d += (uint32_t)__popcll(z & 0x8080808080808080ull);
+        d += (uint32_t)__popcll(slash_bits(load8(blob, b0 + k, end8), len - k) & 0x8080808080808080ull);
       }
     }
     depth[i] = d;
@@ -229,9 +205,7 @@ __global__ __launch_bounds__(kFinT) void k_fin_keys_lds(const uint8_t* __restric
           d = depths_in[i];
         } else {
           for (uint64_t k8 = 0; k8 < len; k8 += 8) {
-            uint64_t z = zero_bytes(key8(k8) ^ 0x2f2f2f2f2f2f2f2full);
-            if (len - k8 < 8) z &= (1ull << (8 * (len - k8))) - 1;
-            d += (uint32_t)__popcll(z & 0x8080808080808080ull);
+            d += (uint32_t)__popcll(slash_bits(key8(k8), len - k8) & 0x8080808080808080ull);
           }
         }
         depth[i] = d;
@@ -413,8 +387,7 @@ struct FinScratch {
   int32_t* smin = nullptr;
   uint32_t* smax = nullptr;
   unsigned* maxd = nullptr;
-  void* tmp = nullptr;
-  size_t tmp_cap = 0;
+  PrimTmp tmp;
   uint64_t cap = 0;
   void release() {
     dfree(lcp);
@@ -424,8 +397,7 @@ struct FinScratch {
     dfree(smin);
     dfree(smax);
     dfree(maxd);
-    dfree(tmp);
-    tmp_cap = 0;
+    tmp.release();
     cap = 0;
   }
 };
@@ -499,12 +471,8 @@ int finalize_device(s3imph_ctx* c, const uint8_t* blob, const uint64_t* offsets,
   rocprim::counting_iterator<uint64_t> iota(0);
   size_t need = 0;
   HIPCHECK(rocprim::radix_sort_pairs(nullptr, need, depth, f.sdepth, iota, depth_positions, n, 0, bits, s));
-  if (need > f.tmp_cap) {
-    dfree(f.tmp);
-    HIPCHECK(hipMalloc(&f.tmp, need));
-    f.tmp_cap = need;
-  }
-  HIPCHECK(rocprim::radix_sort_pairs(f.tmp, need, depth, f.sdepth, iota, depth_positions, n, 0, bits, s));
+  f.tmp.reserve(need);
+  HIPCHECK(rocprim::radix_sort_pairs(f.tmp.p, need, depth, f.sdepth, iota, depth_positions, n, 0, bits, s));
   k_fin_doff<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(f.sdepth, n, md, depth_offsets);
   HIPCHECK(hipGetLastError());
   return S3IMPH_OK;
@@ -523,48 +491,30 @@ int finalize_from_host(int device, const uint8_t* blob, const uint64_t* offsets,
     try {
       HIPCHECK(hipSetDevice(c->device));
       hipStream_t s = c->own_stream;
-      const uint64_t b0 = offsets[0], nbytes = offsets[n] - b0;
       uint8_t* d_blob = nullptr;
       uint64_t *d_offs = nullptr, *d_send = nullptr, *d_dpos = nullptr, *d_doff = nullptr;
       uint32_t *d_depth = nullptr, *d_maxds = nullptr, *d_din = nullptr;
-      struct Guard {
-        std::vector<void*> p;
-        ~Guard() {
-          for (void* q : p)
-            if (q) (void)hipFree(q);
-        }
-      } g;
-      dalloc(d_blob, ((nbytes + 7) & ~7ull) + 16);
-      g.p.push_back(d_blob);
-      dalloc(d_offs, n + 1);
-      g.p.push_back(d_offs);
-      dalloc(d_send, n);
-      g.p.push_back(d_send);
-      dalloc(d_dpos, n);
-      g.p.push_back(d_dpos);
-      dalloc(d_depth, n);
-      g.p.push_back(d_depth);
-      dalloc(d_maxds, n);
-      g.p.push_back(d_maxds);
+      DevGuard g;
+      upload_keys(c, g, blob, offsets, n, d_blob, d_offs);
+      g.make(d_send, n);
+      g.make(d_dpos, n);
+      g.make(d_depth, n);
+      g.make(d_maxds, n);
       if (depths) {
-        dalloc(d_din, n);
-        g.p.push_back(d_din);
+        g.make(d_din, n);
         HIPCHECK(hipMemcpy(d_din, depths, n * 4, hipMemcpyHostToDevice));
       }
-      HIPCHECK(hipMemcpy(d_blob, blob + b0, nbytes, hipMemcpyHostToDevice));
-      staged_copy(c, true, d_offs, offsets, (n + 1) * 8, b0);
       uint64_t cap = 64;
       uint32_t md = 0;
       for (int attempt = 0; attempt < 2; ++attempt) {
-        dalloc(d_doff, cap);
-        g.p.push_back(d_doff);
+        g.make(d_doff, cap);
         int rc = finalize_device(c, d_blob, d_offs, d_din, n, d_depth, d_send, d_maxds, d_dpos, d_doff, cap, &md, s,
                                  msg);
         if (rc == S3IMPH_OK) break;
         if (rc != S3IMPH_ERR_INVALID || attempt) return rc;
         cap = (uint64_t)md + 2;
-        g.p.back() = nullptr;
-        dfree(d_doff);
+        g.drop(d_doff);
+        d_doff = nullptr;
       }
       doff.resize((uint64_t)md + 2);
       HIPCHECK(hipStreamSynchronize(s));

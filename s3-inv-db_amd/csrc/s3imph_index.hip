@@ -29,7 +29,7 @@
 #include <cstring>
 
 #include "s3imph_ctx.h"
-#include "s3imph_device.h"
+#include "s3imph_keys.h"
 #include "s3imph_tiers.h"
 
 namespace s3imph {
@@ -258,31 +258,6 @@ __global__ __launch_bounds__(kScanT) void k_rows_down(const uint64_t* __restrict
 }
 
 // ---- the chunk kernels ---------------------------------------------------------------------
-// First index in [lo, hi) with U[index] > u, or hi.
-__device__ __forceinline__ uint64_t first_above(const uint64_t* __restrict__ U, uint64_t lo, uint64_t hi,
-                                                uint64_t u) {
-  uint64_t len = hi - lo;
-  while (len) {
-    const uint64_t h = len >> 1;
-    const bool right = U[lo + h] <= u;
-    lo = right ? lo + h + 1 : lo;
-    len = right ? len - h - 1 : h;
-  }
-  return lo;
-}
-// First index in [lo, hi) with U[index] >= u, or hi.
-__device__ __forceinline__ uint64_t first_at_least(const uint64_t* __restrict__ U, uint64_t lo, uint64_t hi,
-                                                   uint64_t u) {
-  uint64_t len = hi - lo;
-  while (len) {
-    const uint64_t h = len >> 1;
-    const bool right = U[lo + h] < u;
-    lo = right ? lo + h + 1 : lo;
-    len = right ? len - h - 1 : h;
-  }
-  return lo;
-}
-
 // The rows a chunk [base, end) of the flat list touches (end > base): the row of slot u is
 // the last r with U[r] <= u (empty rows share their successor's start and are never that
 // one); U has n_rows + 1 entries, U[n_rows] = total >= end.

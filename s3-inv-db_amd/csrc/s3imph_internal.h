@@ -555,5 +555,14 @@ bool write_pieces(const std::string& path, size_t count,
 int write_index_files(const std::string& dir, const uint8_t* mph_bin, uint64_t mph_len,
                       const uint64_t* fp, const uint64_t* pos, uint64_t n, const uint8_t* blob,
                       const uint64_t* offsets, std::string* msg);
+// depth.u32, subtree_end.u64, max_depth_in_subtree.u32 and the depth index (n_offsets depth offsets)
+int write_finalize_files(const std::string& dir, const uint32_t* depth, const uint64_t* subtree_end,
+                         const uint32_t* max_depth_sub, const uint64_t* depth_offsets, uint64_t n_offsets,
+                         const uint64_t* depth_positions, uint64_t n, std::string* msg);
+// object_count.u64 / total_bytes.u64
+int write_stats_files(const std::string& dir, const uint64_t* object_count, const uint64_t* total_bytes, uint64_t n,
+                      std::string* msg);
+// manifest.json over the files now in dir (s3imph_manifest.cpp)
+int write_manifest(const std::string& dir, uint64_t node_count, uint32_t max_depth, std::string* msg);
 
 }  // namespace s3imph

@@ -28,21 +28,17 @@
 // the identity without any of this.
 //
 // Gather: lengths in sorted order, one scan into the output offsets, and the key bytes copied by
-// OUTPUT 8-byte word (as k_agg_bytes), so writes are coalesced and a long key is spread over
-// lanes; sizes and tier ids follow the same order.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
+// OUTPUT 8-byte word (emit_word, s3imph_keys.h), so writes are coalesced and a long key is spread
+// over lanes; sizes and tier ids follow the same order.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 #include "s3imph_ctx.h"
-#include "s3imph_device.h"
+#include "s3imph_keys.h"
+#include "s3imph_prim.h"
 
 namespace s3imph {
-
-s3imph_ctx* default_ctx(int device, std::string* msg);
 
 namespace {
 
@@ -53,29 +49,6 @@ constexpr int kST = 256;  // lanes per workgroup: one element / one output word 
 struct SortTop {
   unsigned long long first_unsorted, n_equal, max_len;
 };
-
-// 8 key bytes from blob address a (any alignment); the blob is readable up to end8 =
-// round_up(offsets[m], 8).  (As in s3imph_aggregate.hip.)
-__device__ __forceinline__ uint64_t load8(const uint8_t* blob, uint64_t a, uint64_t end8) {
-  const uint64_t al = a & ~7ull;
-  const uint64_t* w = reinterpret_cast<const uint64_t*>(blob + al);
-  const uint64_t lo = w[0];
-  const uint64_t hi = (a & 7) && al + 8 < end8 ? w[1] : 0;
-  return (a & 7) ? funnel_bytes(lo, hi, (unsigned)(a & 7)) : lo;
-}
-
-// First index in [lo, hi) with U[index] > u, or hi.
-__device__ __forceinline__ uint64_t first_above(const uint64_t* __restrict__ U, uint64_t lo, uint64_t hi,
-                                                uint64_t u) {
-  uint64_t len = hi - lo;
-  while (len) {
-    const uint64_t h = len >> 1;
-    const bool right = U[lo + h] <= u;
-    lo = right ? lo + h + 1 : lo;
-    len = right ? len - h - 1 : h;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 #pragma unroll
@@ -243,55 +216,23 @@ __global__ __launch_bounds__(kST) void k_gather_meta(const uint64_t* __restrict_
   if (tiers) tiers_out[j] = tiers[i];
 }
 
-// The owner (sorted key) of each output chunk's first word: one lane per chunk (as k_agg_bounds).
-// out[t] = last index with U[index] <= t * step.
+// The owner (sorted key) of each output chunk's first word: one lane per chunk (chunk_owner).
 __global__ __launch_bounds__(kST) void k_gather_bounds(const uint64_t* __restrict__ U, uint64_t entries,
                                                        uint64_t step, uint64_t nchunks,
                                                        uint64_t* __restrict__ out) {
   const uint64_t t = (uint64_t)blockIdx.x * kST + threadIdx.x;
-  if (t < nchunks) out[t] = first_above(U, 0, entries, t * step) - 1;
+  if (t < nchunks) out[t] = chunk_owner(U, entries, step, 0, t);
 }
 
-// Gather, second half, by output bytes: each lane assembles one 8-byte word of the sorted blob.
-// The key of a byte is the last one that starts at or before it; its source is the same distance
-// into input key order[j].  One unaligned 8-byte read of the input blob per key the word
-// overlaps.  Bytes past `total` in the last word are zeros.
+// Gather, second half, by output bytes (emit_word): each lane assembles one 8-byte word of the
+// sorted blob; the source of output key r is input key order[r].
 __global__ __launch_bounds__(kST) void k_gather_bytes(const uint8_t* __restrict__ blob, uint64_t key_end8,
                                                       const uint64_t* __restrict__ offsets,
                                                       const uint32_t* __restrict__ order,
                                                       const uint64_t* __restrict__ off_out,
                                                       const uint64_t* __restrict__ bounds, uint64_t m,
                                                       uint64_t total, uint8_t* __restrict__ out) {
-  const uint64_t wbase = (uint64_t)blockIdx.x * kST;
-  const uint64_t nw = (total + 7) / 8;
-  if (wbase >= nw) return;
-  // off_out has m + 1 entries, off_out[0] = 0, off_out[m] = total
-  const uint64_t r_lo = bounds[blockIdx.x];
-  const uint64_t r_hi = blockIdx.x + 1 < gridDim.x ? bounds[blockIdx.x + 1] : m - 1;
-  const uint64_t wi = wbase + threadIdx.x;
-  if (wi >= nw) return;
-  const uint64_t a = 8 * wi, aend = min(a + 8, total);
-  uint64_t r = first_above(off_out, r_lo + 1, r_hi + 1, a) - 1;
-  uint64_t o0 = off_out[r], o1 = off_out[r + 1];
-  uint64_t v = 0;
-  for (uint64_t p = a; p < aend;) {
-    while (o1 <= p) {  // off_out[m] = total > p ends it
-      ++r;
-      o0 = o1;
-      o1 = off_out[r + 1];
-    }
-    const uint64_t cnt = min(o1, aend) - p;  // bytes of key r in this word, 1..8
-    // the read may run past the key, never past the blob's readable end
-    const uint64_t x = load8(blob, offsets[order[r]] + (p - o0), key_end8);
-    v |= (cnt >= 8 ? x : x & ((1ull << (8 * cnt)) - 1)) << (8 * (p - a));
-    p += cnt;
-  }
-  if (((uintptr_t)out & 7) == 0) {
-    *reinterpret_cast<uint64_t*>(out + a) = v;
-  } else {
-#pragma unroll
-    for (int b = 0; b < 8; ++b) out[a + b] = (uint8_t)(v >> (8 * b));
-  }
+  emit_word<kST>(blob, key_end8, off_out, bounds, m, total, out, [&](uint64_t r) { return offsets[order[r]]; });
 }
 
 }  // namespace
@@ -307,8 +248,7 @@ struct SortScratch {
   unsigned long long* bad = nullptr;  // the gather's first order entry out of range
   uint64_t* bounds = nullptr;         // the gather chunks' first keys
   uint64_t bounds_cap = 0;
-  void* tmp = nullptr;
-  size_t tmp_cap = 0;
+  PrimTmp tmp;
   void release() {
     for (int b = 0; b < 2; ++b) {
       dfree(packed[b]);
@@ -320,9 +260,8 @@ struct SortScratch {
     dfree(top);
     dfree(bad);
     dfree(bounds);
-    dfree(tmp);
+    tmp.release();
     cap = bounds_cap = 0;
-    tmp_cap = 0;
   }
 };
 
@@ -335,31 +274,6 @@ void sort_scratch_free(s3imph_ctx* c) {
 }
 
 namespace {
-
-void need_tmp(SortScratch& a, size_t need) {
-  if (need > a.tmp_cap) {
-    dfree(a.tmp);
-    a.tmp_cap = 0;
-    HIPCHECK(hipMalloc(&a.tmp, need));
-    a.tmp_cap = need;
-  }
-}
-
-void scan_u64(SortScratch& a, uint64_t* v, uint64_t count, hipStream_t s) {
-  size_t need = 0;
-  HIPCHECK(rocprim::exclusive_scan(nullptr, need, v, v, (uint64_t)0, count, rocprim::plus<uint64_t>(), s));
-  need_tmp(a, need);
-  HIPCHECK(rocprim::exclusive_scan(a.tmp, need, v, v, (uint64_t)0, count, rocprim::plus<uint64_t>(), s));
-}
-
-// (b) One stable radix sort of `count` (key, value) pairs on the key bits [lo, hi).
-void sort_pairs(SortScratch& a, const uint64_t* kin, uint64_t* kout, const uint64_t* vin, uint64_t* vout,
-                uint64_t count, unsigned lo, unsigned hi, hipStream_t s) {
-  size_t need = 0;
-  HIPCHECK(rocprim::radix_sort_pairs(nullptr, need, kin, kout, vin, vout, (size_t)count, lo, hi, s));
-  need_tmp(a, need);
-  HIPCHECK(rocprim::radix_sort_pairs(a.tmp, need, kin, kout, vin, vout, (size_t)count, lo, hi, s));
-}
 
 unsigned blocks(uint64_t count) { return (unsigned)((count + kST - 1) / kST); }
 
@@ -430,19 +344,19 @@ int sort_objects(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, uint6
     k_sort_words<<<blocks(active), kST, 0, s>>>(keys, koff, m, act, active, 7ull * round, a.word[0]);
     HIPCHECK(hipGetLastError());
     // stable by word, then stable by segment: ordered by (segment, word, input index)
-    sort_pairs(a, a.word[0], a.word[1], act, oth, active, 0, 64, s);
+    sort_pairs(a.tmp, a.word[0], a.word[1], act, oth, active, 0, 64, s);
     uint64_t *pk = oth, *wd = a.word[1], *next = act;  // the sorted set, and the buffer now free
     if (segs > 1) {
       unsigned bits = 1;
       while (bits < 32 && ((segs - 1) >> bits)) ++bits;
-      sort_pairs(a, oth, act, a.word[1], a.word[0], active, 32, 32 + bits, s);
+      sort_pairs(a.tmp, oth, act, a.word[1], a.word[0], active, 32, 32 + bits, s);
       pk = act;
       wd = a.word[0];
       next = oth;
     }
     k_sort_mark<<<blocks(active + 1), kST, 0, s>>>(pk, wd, a.delta[cur], active, order, a.fpos, a.v, a.top);
     HIPCHECK(hipGetLastError());
-    scan_u64(a, a.v, active + 1, s);
+    scan_u64(a.tmp, a.v, active + 1, 0, s);
     k_sort_compact<<<blocks(active), kST, 0, s>>>(pk, a.fpos, a.v, active, next, a.delta[cur ^ 1]);
     HIPCHECK(hipGetLastError());
     uint64_t tot = 0;
@@ -481,7 +395,7 @@ int gather_objects(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, con
   HIPCHECK(hipMemsetAsync(a.bad, 0xff, 8, s));
   k_gather_meta<<<blocks(m + 1), kST, 0, s>>>(koff, sizes, tiers, m, order, off_out, sizes_out, tiers_out, a.bad);
   HIPCHECK(hipGetLastError());
-  scan_u64(a, off_out, m + 1, s);
+  scan_u64(a.tmp, off_out, m + 1, 0, s);
   unsigned long long bad = 0;
   uint64_t total = 0, key_end = 0;
   HIPCHECK(hipMemcpyAsync(&bad, a.bad, 8, hipMemcpyDeviceToHost, s));
@@ -503,11 +417,7 @@ int gather_objects(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, con
       return S3IMPH_ERR_INVALID;
     }
     const uint64_t chunks = (nw + kST - 1) / kST;
-    if (chunks > a.bounds_cap) {
-      a.bounds_cap = 0;
-      dalloc(a.bounds, chunks);
-      a.bounds_cap = chunks;
-    }
+    grow(a.bounds, a.bounds_cap, chunks);
     k_gather_bounds<<<blocks(chunks), kST, 0, s>>>(off_out, m + 1, 8ull * kST, chunks, a.bounds);
     k_gather_bytes<<<(unsigned)chunks, kST, 0, s>>>(keys, (key_end + 7) & ~7ull, koff, order, off_out, a.bounds, m,
                                                     total, keys_out);
@@ -567,8 +477,7 @@ int s3imph_gather_objects_device(s3imph_ctx* c, const uint8_t* d_keys, const uin
 
 int s3imph_sort_objects_host(int device, const uint8_t* keys, const uint64_t* key_offsets, uint64_t m,
                              uint32_t** order, s3imph_sort_info* info, char* err, size_t errlen) {
-  if (!order || !info || (m >> 32) || (m && (!key_offsets || (!keys && key_offsets[m] != key_offsets[0]))))
-    return S3IMPH_ERR_INVALID;
+  if (!order || !info || (m >> 32) || !listing_given(keys, key_offsets, m)) return S3IMPH_ERR_INVALID;
   *order = nullptr;
   std::memset(info, 0, sizeof *info);
   info->first_unsorted = UINT64_MAX;
@@ -590,25 +499,12 @@ int s3imph_sort_objects_host(int device, const uint8_t* keys, const uint64_t* ke
     HIPCHECK(hipSetDevice(c->device));
     hipStream_t s = c->own_stream;
     const int rc = retry_on_nomem(c, s, &msg, [&]() -> int {
+      DevGuard g;
       uint8_t* d_keys = nullptr;
       uint64_t* d_koff = nullptr;
       uint32_t* d_order = nullptr;
-      struct Drop {
-        uint8_t*& k;
-        uint64_t*& o;
-        uint32_t*& r;
-        ~Drop() {
-          dfree(k);
-          dfree(o);
-          dfree(r);
-        }
-      } drop{d_keys, d_koff, d_order};
-      const uint64_t b0 = key_offsets[0], nbytes = key_offsets[m] - b0;
-      dalloc(d_keys, ((nbytes + 7) & ~7ull) + 16);
-      dalloc(d_koff, m + 1);
-      dalloc(d_order, m);
-      if (nbytes) HIPCHECK(hipMemcpy(d_keys, keys + b0, nbytes, hipMemcpyHostToDevice));
-      staged_copy(c, true, d_koff, key_offsets, (m + 1) * 8, b0);
+      upload_keys(c, g, keys, key_offsets, m, d_keys, d_koff);
+      g.make(d_order, m);
       const int rc2 = sort_objects(c, d_keys, d_koff, m, d_order, info, s, &msg);
       if (rc2 != S3IMPH_OK) return rc2;
       staged_copy(c, false, out, d_order, m * 4);

@@ -141,6 +141,17 @@ def test_keys_longer_than_32k(ctx):
     check(ctx, keys, max_depth=2, align=5, what="long keys, depth 2")
 
 
+def test_rows_at_the_byte_emit_chunk_edges(ctx):
+    """The byte emit writes the prefix blob in chunks of 256 words (2048 bytes), one workgroup each:
+    rows of 1 to 9 bytes (up to three inside one word), a row that ends exactly on the chunk edge at
+    byte 2048, a row that owns a whole chunk, a blob length that is no multiple of 8."""
+    keys = [b"/////////x", b"a" * 2002 + b"/x", b"b/c/d/e/f/g/h/i/x", b"c" * 4200 + b"/y/z"]
+    want = check(ctx, keys, [5, 1 << 40, 7, (1 << 64) - 3], what="chunk edges")
+    assert want[1].tolist() == [0, 0, 1, 3, 6, 10, 15, 21, 28, 36, 45, 2048, 2050, 2054, 2060, 2068, 2078, 2090,
+                                2104, 2120, 6321, 10524]
+    check(ctx, keys, align=3, what="chunk edges, misaligned keys")
+
+
 def random_keys(rng, m, max_len=9, alphabet=b"ab/!~\xc3"):
     alpha = np.frombuffer(alphabet, np.uint8)
     return sorted(bytes(alpha[rng.integers(0, len(alpha), rng.integers(0, max_len))]) for _ in range(m))

@@ -237,6 +237,54 @@ def test_gather_matches_numpy_indexing(ctx, gathered):
     assert agg["first_unsorted"] == 2**64 - 1 and agg["n_objects"] == m
 
 
+CHUNK = 2048  # bytes of output one workgroup of the byte emit writes: 256 words
+
+# output key lengths, in output order: a key that ends exactly on the chunk edge at byte 2048, two
+# empty keys on that edge, nine keys inside two words, a key that owns all of chunk 2 and chunk 3's
+# start (a workgroup whose first and last owner are the same key), an empty last key, 6164 bytes in
+# all (no multiple of 8); then exactly one chunk, and one chunk plus one byte
+CHUNK_EDGE_LAYOUTS = {
+    "edges": [2040, 3, 0, 5, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 4100, 0, 7, 0],
+    "one_chunk": [0, 2047, 1, 0],
+    "one_chunk_and_a_byte": [0, 2047, 1, 1, 0],
+}
+
+
+@pytest.mark.parametrize("name", CHUNK_EDGE_LAYOUTS, ids=list(CHUNK_EDGE_LAYOUTS))
+def test_gather_at_chunk_edges(ctx, name):
+    """The output layout is chosen here, not left to the sort: the order is a seeded permutation
+    and the input listing is the wanted output scattered by it."""
+    import torch
+    lens = CHUNK_EDGE_LAYOUTS[name]
+    m = len(lens)
+    rng = np.random.default_rng(21)
+    want_keys = [rng.integers(1, 256, n, dtype=np.uint8).tobytes() for n in lens]
+    order = rng.permutation(m).astype(np.uint32)  # order[j] = input index of the j-th output key
+    keys = [b""] * m
+    for j, i in enumerate(order):
+        keys[i] = want_keys[j]
+    sizes = rng.integers(0, 1 << 63, m, dtype=np.uint64)
+    tiers = rng.integers(0, s3imph.NUM_TIERS, m, dtype=np.uint8)
+    blob, offs = O.keys_to_blob(want_keys)
+    assert offs.tolist() == [0] + np.cumsum(lens).tolist()
+    if name == "edges":
+        assert len(blob) == 6164 and offs[4] == CHUNK
+        owners = np.searchsorted(offs, np.arange(4) * CHUNK, side="right") - 1
+        assert owners.tolist() == [0, 6, 16, 16]
+    else:
+        assert len(blob) == CHUNK + (name != "one_chunk")
+    d_keys, d_offs, d_sizes, d_tiers = to_dev(keys, sizes, tiers)
+    d_order = torch.from_numpy(order.view(np.int32).copy()).to("cuda")
+    out = ctx.gather_objects(d_keys, d_offs, m, d_order, d_sizes=d_sizes, d_tiers=d_tiers)
+    assert np.array_equal(out["offsets"].cpu().numpy().view(np.uint64), offs)
+    raw = out["keys"].cpu().numpy()
+    assert len(raw) == (len(blob) + 7) // 8 * 8 and out["key_bytes"] == len(blob)
+    assert np.array_equal(raw[:len(blob)], blob)
+    assert not raw[len(blob):].any(), "the padding up to 8 bytes must be zeros"
+    assert np.array_equal(out["sizes"].cpu().numpy().view(np.uint64), sizes[order])
+    assert np.array_equal(out["tiers"].cpu().numpy(), tiers[order])
+
+
 def test_gather_without_sizes_and_tiers_and_into_a_misaligned_blob(ctx, gathered):
     import torch
     g = gathered
