@@ -310,9 +310,6 @@ struct P0Part {
   uint64_t reg_cap;  // records per (hash block, super-tile) region
   unsigned* pcnt;    // region fills, written at each block's end
   unsigned tps, S;
-  // overlapped scatter (k_scatter_p0d<kOv>, beside this kernel): each block's XCD, published
-  // with its fills once its region runs are in that XCD's L2; null: no publication
-  unsigned* hxcc = nullptr;
 };
 template <int NT, int BB, bool PF, bool RT = false, bool PT = false>
 __global__ __launch_bounds__(NT, 2048 / NT * NT / 256 / 2) void k_hash0_pair(const uint8_t* __restrict__ blob,
@@ -335,10 +332,7 @@ __global__ __launch_bounds__(NT, 2048 / NT * NT / 256 / 2) void k_hash0_pair(con
   constexpr int KW = (BB / 16 + NT - 1) / NT;  // 16-byte window chunks per thread
   constexpr unsigned kLB = 256;                // length classes of the sort
   constexpr int NW = NT / 64;
-  // S3IMPH_FNV_PAIR: the window starts kWP words in, so >= 8 bytes precede every key (the
-  // zero-prefixed first word of fnv_window_pair reads them, masked)
-  constexpr unsigned kWP = S3IMPH_FNV_PAIR ? 2u : 0u;
-  __shared__ uint64_t sw[BB / 8 + 2 + kWP];    // the round's window (+ 16 B: a lane may read one word past)
+  __shared__ uint64_t sw[BB / 8 + 2];          // the round's window (+ 16 B: a lane may read one word past)
   // sorted slot -> key's window offset (< BB) | length (<= BB) << 16: one LDS word per key
   static_assert(BB <= 32768, "offset and length in 16 bits each");
   __shared__ unsigned sol[G];
@@ -351,15 +345,8 @@ __global__ __launch_bounds__(NT, 2048 / NT * NT / 256 / 2) void k_hash0_pair(con
   __shared__ uint64_t r_base[RT || PT ? kMaxRanks : 1];
   __shared__ unsigned r_over;
   __shared__ unsigned p_cur[PT ? kMaxRanks : 1];  // PT: this block's fill of each super-tile region
-  __shared__ uint64_t s_fnv_init[S3IMPH_FNV_PAIR ? 8 : 1];  // fnv_prefixed_basis(pad), pad 0..7
   if (st->skew) return;  // k_hash_count0 hashes skewed sets (and clears the tile state)
   const unsigned tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-  if (S3IMPH_FNV_PAIR && tid < 8) {  // (ordered before the first hash by the round's barriers)
-    constexpr uint64_t kInit[8] = {fnv_prefixed_basis(0), fnv_prefixed_basis(1), fnv_prefixed_basis(2),
-                                   fnv_prefixed_basis(3), fnv_prefixed_basis(4), fnv_prefixed_basis(5),
-                                   fnv_prefixed_basis(6), fnv_prefixed_basis(7)};
-    s_fnv_init[tid] = kInit[tid];
-  }
   static_assert(!RT || G * sizeof(Rec) + G <= sizeof(sw), "the route stage aliases the byte window");
   // RT: level 0's geometry and owner ranges; this rank's own-record shift (records received
   // for earlier key chunks sit before its own ones)
@@ -398,21 +385,10 @@ __global__ __launch_bounds__(NT, 2048 / NT * NT / 256 / 2) void k_hash0_pair(con
       for (uint64_t q = g0; q < kTcntWords; q += gs) tcnt[q] = 0;
     }
   }
-  // overlap: this block's XCD at once (the overlapped scatter learns which hash blocks share
-  // its XCD from the first ones: the dispatcher deals blocks to the XCDs round-robin)
-  if (PT && pt.hxcc && tid == 0) __hip_atomic_store(&pt.hxcc[bid], xcc_id(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const uint64_t per = (n + NBK - 1) / NBK;
   uint64_t g = (uint64_t)bid * per;
   const uint64_t gend = min(n, g + per);
   if (g >= gend) {
-    if (PT && pt.hxcc) {  // (no region runs: published at once)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __syncthreads();
-      if (tid < pt.S) __hip_atomic_store(&pt.pcnt[(uint64_t)bid * pt.S + tid], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __syncthreads();
-      if (tid == 0) __hip_atomic_fetch_add(&st->h0_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
     if (PT && tid < pt.S) pt.pcnt[(uint64_t)bid * pt.S + tid] = 0;
     return;
   }
@@ -459,13 +435,13 @@ __global__ __launch_bounds__(NT, 2048 / NT * NT / 256 / 2) void k_hash0_pair(con
     for (int k = 0; k < KW; ++k) {
       const unsigned c = tid + (unsigned)k * NT;
       if (c < nfull) {
-        sw[kWP + 2 * c] = (uint64_t)wr[k].x | ((uint64_t)wr[k].y << 32);
-        sw[kWP + 2 * c + 1] = (uint64_t)wr[k].z | ((uint64_t)wr[k].w << 32);
+        sw[2 * c] = (uint64_t)wr[k].x | ((uint64_t)wr[k].y << 32);
+        sw[2 * c + 1] = (uint64_t)wr[k].z | ((uint64_t)wr[k].w << 32);
       }
     }
     if (tail8 && tid == 0) {  // once per blob: the last 8 readable bytes (a blocking load)
-      sw[kWP + 2 * nfull] = *reinterpret_cast<const uint64_t*>(blob + (end8 - 8));
-      sw[kWP + 2 * nfull + 1] = 0;
+      sw[2 * nfull] = *reinterpret_cast<const uint64_t*>(blob + (end8 - 8));
+      sw[2 * nfull + 1] = 0;
     }
     for (unsigned b = tid; b < kLB; b += NT) lcnt[b] = 0;
     if ((RT || PT) && tid < kMaxRanks) r_cnt[tid] = 0;
@@ -522,7 +498,7 @@ __global__ __launch_bounds__(NT, 2048 / NT * NT / 256 / 2) void k_hash0_pair(con
       if (fits[h]) {
         const unsigned slot = lcnt[cls[h]] + rk[h];
         sidx[slot] = (unsigned short)(tid + (unsigned)h * NT);
-        sol[slot] = ((unsigned)(t_b0[h] - rw) + 8u * kWP) | ((unsigned)(t_b1[h] - t_b0[h]) << 16);
+        sol[slot] = (unsigned)(t_b0[h] - rw) | ((unsigned)(t_b1[h] - t_b0[h]) << 16);
       }
     __syncthreads();
     const uint64_t r0 = g;
@@ -548,19 +524,6 @@ __global__ __launch_bounds__(NT, 2048 / NT * NT / 256 / 2) void k_hash0_pair(con
           fp[r0] = b;
         }
         zero |= (a == 0);
-      }
-    } else if (S3IMPH_FNV_PAIR) {
-      // the lane's two keys as one word loop (fnv_window_pair)
-      const bool vA = tid < (m + 1) / 2, vB = tid < m / 2;
-      if (vA) {
-        const unsigned olA = sol[tid], olB = vB ? sol[m - 1 - tid] : 0u;
-        rj[0] = sidx[tid];
-        rj[1] = vB ? sidx[m - 1 - tid] : 0u;
-        fnv_window_pair(reinterpret_cast<const uint32_t*>(sw), olA & 0xffffu, olA >> 16, olB & 0xffffu, olB >> 16, vB,
-                        s_fnv_init, ra[0], rb[0], ra[1], rb[1]);
-        rv[0] = true;
-        rv[1] = vB;
-        zero |= ra[0] == 0 || (vB && ra[1] == 0);
       }
     } else {
 #pragma unroll
@@ -713,18 +676,6 @@ __global__ __launch_bounds__(NT, 2048 / NT * NT / 256 / 2) void k_hash0_pair(con
   if (zero) atomicOr(&st->status, kStKeyZero);
   if (RT && tid == 0 && r_over) atomicOr(&st->status, kStRouteOverflow);
   if (PT && tid == 0 && r_over) atomicOr(&st->status, kStOverflow | kStResOverflow);
-  if (PT && pt.hxcc) {
-    // publication for the overlapped scatter, which reads this block's regions through the
-    // same XCD's L2 while the hash runs on: every thread's region stores complete (in L2)
-    // before the barrier, the fills after it, then the block counts as done
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (tid < pt.S)
-      __hip_atomic_store(&pt.pcnt[(uint64_t)bid * pt.S + tid], p_cur[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(&st->h0_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
   if (PT && tid < pt.S) pt.pcnt[(uint64_t)bid * pt.S + tid] = p_cur[tid];  // wave 0 updated p_cur
 }
 
@@ -750,52 +701,40 @@ constexpr int kSkS = kSkC + 16;        // LDS stride per key (16-B aligned for d
 constexpr int kSkU = kSkC / 16;        // 16-byte units per key chunk = loads per step
 constexpr unsigned kSkLB = 256;        // length classes (4 B each)
 // kSkT threads, kSkG keys per sorted group: 768 / 5120 (one block per CU, three waves per
-// SIMD), 1024 / 4096 (four waves per SIMD) or 512 / 2048 (two blocks per CU: one block's
-// sort and group barrier overlap the other's hashing).  A group's makespan is at least its
-// longest batch (C5: 16 chunk steps for 1024-byte keys); 4096 keys give each of 16 waves
-// ~12.5 steps on average, so the group barrier waited ~17 % of a wave's life; 5120 keys
-// over 12 waves give ~21 (C5 hash 1.65-1.66 -> 1.60-1.62 ms, `profiles/r3_skew*/`; 11, 10 and
-// 13 waves, and 8 waves with 4096 keys, measured slower).
-// kRes false: the partition form only (P0's level 0, pt.sup set), whose records leave for
-// their super-tile regions as each batch ends: no per-key result arrays in LDS, so two
-// blocks fit a CU with 5120-key groups (S3IMPH_SKEW_CFG 3; 16 waves per CU instead of 12).
+// SIMD).  A group's makespan is at least its longest batch (C5: 16 chunk steps for 1024-byte
+// keys); 4096 keys gave each of 16 waves ~12.5 steps on average, so the group barrier waited
+// ~17 % of a wave's life; 5120 keys over 12 waves give ~21 (C5 hash 1.65-1.66 -> 1.60-1.62 ms,
+// `profiles/r3_skew*/`; 11, 10 and 13 waves, 8 waves with 4096 keys, and two 512-thread blocks
+// per CU with 2048-key groups or with the partition form's 5120, measured slower).
 template <int kSkT, int kSkG>
 constexpr size_t sk_stage_bytes() { return (size_t)(kSkT / 64) * 64 * kSkS; }
-template <int kSkT, int kSkG, bool kRes = true>
+template <int kSkT, int kSkG>
 constexpr size_t sk_lds_bytes() {
-  return sk_stage_bytes<kSkT, kSkG>() + (kRes ? 2 * kSkG * sizeof(uint64_t) : 0) + kSkG * sizeof(unsigned short) +
+  return sk_stage_bytes<kSkT, kSkG>() + 2 * kSkG * sizeof(uint64_t) + kSkG * sizeof(unsigned short) +
          kSkLB * sizeof(unsigned) + 16;
 }
-static_assert(sk_lds_bytes<1024, 4096>() <= 160 * 1024, "k_hash_skew's LDS");
-static_assert(2 * sk_lds_bytes<512, 2048>() <= 160 * 1024, "k_hash_skew's LDS, two blocks per CU");
 static_assert(sk_lds_bytes<768, 5120>() <= 160 * 1024, "k_hash_skew's LDS, 12 waves");
-static_assert(2 * sk_lds_bytes<512, 5120, false>() <= 160 * 1024, "k_hash_skew's LDS, partition form, two blocks per CU");
 static_assert(kSkU * 16 == 64, "a load instruction covers 16 keys x 64 B");
 
-template <int kSkT, int kSkG, bool kRes = true>
+template <int kSkT, int kSkG>
 __global__ __launch_bounds__(kSkT, 4) void k_hash_skew(const uint8_t* __restrict__ blob,
                                                        const uint64_t* __restrict__ offsets, uint64_t n,
                                                        uint64_t* __restrict__ kh, uint64_t* __restrict__ fp,
                                                        unsigned long long* __restrict__ flags,
                                                        unsigned long long* __restrict__ sflags, LevelState* st,
                                                        unsigned tb, uint64_t chunk, unsigned* __restrict__ tcnt,
-                                                       unsigned long long* __restrict__ prof, int order,
+                                                       unsigned long long* __restrict__ prof,
                                                        P0Part pt = P0Part{}) {
   extern __shared__ __align__(16) unsigned char sk_lds[];
   // pt.sup (P0's level 0): each group's records (R20) go to this block's region of their
   // super-tile through an LDS cursor per super-tile, instead of kh / fp in key order
   __shared__ unsigned sk_pcur[kMaxRanks];
   if (!st->skew) return;  // k_hash0_pair hashed this near-uniform set
-  const bool part = kRes ? pt.sup != nullptr : true;
-  if (!kRes && pt.sup == nullptr) {  // (the host launches the partition form only with regions)
-    if (threadIdx.x == 0) atomicOr(&st->status, kStGeometry);
-    return;
-  }
+  const bool part = pt.sup != nullptr;
   const uint32_t p_mul = part ? 0xffffffffu / pt.tps + 1 : 0u;
   const uint64_t p_words = st->words[0], p_magic = st->magic[0];
   bool p_over = false;
   if (part && threadIdx.x < kMaxRanks) sk_pcur[threadIdx.x] = 0;  // (the first group's barriers order it)
-  const bool interleave = order == 0;
   // prof (S3IMPH_DEBUG): per wave, shader cycles total / hashing / waiting for a chunk's
   // loads / the rest (sort, tickets, barriers, write-back)
   const unsigned long long pt0 = __builtin_amdgcn_s_memtime(), prt0 = __builtin_amdgcn_s_memrealtime();
@@ -803,8 +742,8 @@ __global__ __launch_bounds__(kSkT, 4) void k_hash_skew(const uint8_t* __restrict
   uint4* stage = reinterpret_cast<uint4*>(sk_lds);
   constexpr size_t kSkStage = sk_stage_bytes<kSkT, kSkG>();
   uint64_t* res_a = reinterpret_cast<uint64_t*>(sk_lds + kSkStage);
-  uint64_t* res_b = res_a + (kRes ? kSkG : 0);
-  unsigned short* sidx = reinterpret_cast<unsigned short*>(res_b + (kRes ? kSkG : 0));
+  uint64_t* res_b = res_a + kSkG;
+  unsigned short* sidx = reinterpret_cast<unsigned short*>(res_b + kSkG);
   unsigned* cnt = reinterpret_cast<unsigned*>(sidx + kSkG);
   unsigned* next = cnt + kSkLB;
   const unsigned tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
@@ -899,9 +838,9 @@ __global__ __launch_bounds__(kSkT, 4) void k_hash_skew(const uint8_t* __restrict
       unsigned t = 0;
       if (lane == 0) t = atomicAdd(next, 1u);
       t = __shfl(t, 0);
-      // longest batch first (LPT); the alternative alternates the longest and the shortest
-      // batch left (measured worse on C5: the group barrier waited 33 % vs 17 %)
-      x.b = t >= nb ? nb : (!interleave ? t : (t & 1u) ? nb - 1 - (t >> 1) : (t >> 1));
+      // longest batch first (LPT; alternating the longest and the shortest batch left measured
+      // worse on C5: the group barrier waited 33 % vs 17 %)
+      x.b = min(t, nb);
       if (x.b >= nb) return;
       const int hi = (int)m - 64 * (int)x.b;  // sorted slots [hi - 64, hi)
       const int slot = hi - 64 + (int)lane;
@@ -936,11 +875,7 @@ __global__ __launch_bounds__(kSkT, 4) void k_hash_skew(const uint8_t* __restrict
         const uint32_t a = x.lb[t] + step * kSkC + 16u * u;
         const bool in = a < x.le[t], full = (uint64_t)a + 16 <= end8r;
         uint4 v = make_uint4(0, 0, 0, 0);
-#if S3IMPH_NT_SKEW
-        if (in && full) v = ld_stream16(gblob + a);
-#else
         if (in && full) v = *reinterpret_cast<const uint4*>(gblob + a);
-#endif
         if (in && !full) {
           const uint64_t h = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(gblob + a));
           v = make_uint4((uint32_t)h, (uint32_t)(h >> 32), 0u, 0u);
@@ -1006,7 +941,7 @@ __global__ __launch_bounds__(kSkT, 4) void k_hash_skew(const uint8_t* __restrict
             pt.sup[((uint64_t)blockIdx.x * pt.S + od) * pt.reg_cap + at] = r20_make(a, f, (uint32_t)(grp + cur.k));
           else
             p_over = true;
-        } else if (kRes) {
+        } else {
           // results by key in LDS, written back in key order with coalesced stores (each
           // lane's own 8-byte stores cost more: they count against vmcnt, which every step
           // waits on, 1.64 -> 2.11 ms on C5 even with 8192-key groups in the freed LDS)
@@ -1018,8 +953,12 @@ __global__ __launch_bounds__(kSkT, 4) void k_hash_skew(const uint8_t* __restrict
     }
     const unsigned long long e0t = prof ? __builtin_amdgcn_s_memtime() : 0;
     __syncthreads();
-    if (kRes && !part) {
-      for (unsigned k = tid; k < m; k += kSkT) {
+    if (!part) {
+      // (the thread index opaque here: the result arrays' LDS address is recomputed per group,
+      // not hoisted out of the group loop and spilled)
+      unsigned me = tid;
+      asm volatile("" : "+v"(me));
+      for (unsigned k = me; k < m; k += kSkT) {
         const uint64_t a = res_a[k];
         kh[grp + k] = a;
         fp[grp + k] = res_b[k];
@@ -1755,214 +1694,6 @@ __global__ __launch_bounds__(NT) void k_scatter_p0(P0In in, unsigned bps, unsign
   }
 #undef P0PROF
   if (geo) (atomicOr(&st->status, kStGeometry), atomicCAS(&st->pad0_, 0u, 5u));
-  if (s_over && tid == 0) atomicOr(&st->status, kStOverflow | kStResOverflow);
-}
-
-// ---- the super-tile scatter, direct form; overlapped with the level-0 hash --------------
-// A round's records stay in registers and go straight to their tiles' slots: LDS holds only
-// the per-tile counts and run bases (~5 KB), so a block fits beside three hash blocks on a CU.
-// A super-tile's records are cut into parts by hash block: part x C + c (XCD x, chunk c)
-// holds the regions of hash blocks x + 8 (c R + i), i < R = NB / 8C, and its records take
-// reservation shard x.
-// kOv: persistent blocks launched beside the level-0 hash (k_hash0_pair with P0Part::hxcc).
-// A block takes the parts of the residue class of hash blocks that runs on its own XCD (the
-// dispatcher deals a launch's blocks to the XCDs round-robin, from a varying first XCD: the
-// class is learned from the first eight hash blocks' published XCDs, each part's checked) by
-// ticket, chunk-major, and waits for the part's hash blocks: they wrote their region runs through its L2, so their fills — published with agent-scope
-// stores after a workgroup release — make the runs readable here without an L2 write-back.  A
-// part whose hash blocks ran elsewhere or are not done within the spin bound, and every part
-// still open when the hash has finished, is left to the follow-up launch (!kOv: one block per
-// (super-tile, part), after the hash, so across a kernel boundary), which skips the parts the
-// overlapped launch marked done.
-struct P0Ov {
-  const unsigned* hxcc = nullptr;  // each hash block's XCD (kOv)
-  unsigned* done = nullptr;        // [part][super-tile] scattered by the overlapped launch
-  unsigned C = 8;                  // chunks per XCD
-};
-constexpr int kDT = 256;
-constexpr int kDU = 16;                       // records per thread and round (4096 per round)
-constexpr unsigned kPcntOpen = 0xffffffffu;   // a region fill not yet published
-constexpr unsigned kOvSpin = 1u << 20;        // wait rounds for a part's hash blocks (~s_sleep 8 each)
-
-template <int kT, bool kOv>
-__global__ __launch_bounds__(kDT) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_scatter_p0d(P0In in, unsigned tps, R20* __restrict__ bucket, uint64_t bcap,
-                                                     unsigned* __restrict__ tcnt, unsigned long long* __restrict__ flags,
-                                                     LevelState* st, P0Ov ov) {
-  __shared__ unsigned cnt[kT];
-  __shared__ unsigned cur[kT];
-  __shared__ unsigned rp[65];
-  __shared__ unsigned s_item, s_ok, s_over;
-  if (st->status & kStStop) return;
-  const unsigned tid = threadIdx.x, lane = lane_id();
-  const uint64_t words = st->words[0], magic = st->magic[0];
-  const uint64_t T = tiles_of(words, kRegTileMaxBits, 0);
-  const bool skw = st->skew != 0;
-  if (kOv && skw) return;  // the skewed hash's regions come after this launch: the follow-up's
-  if (!kOv) {
-    if (blockIdx.x == 0 && tid == 0) {
-      st->ntiles[0] = T;
-      st->nchunks[0] = 0;
-    }
-    for (uint64_t t = (uint64_t)blockIdx.x * kDT + tid; t < T; t += (uint64_t)gridDim.x * kDT) flags[t] = 0;
-  }
-  const unsigned NB = skw ? in.NB_skew : in.NB;
-  const uint64_t reg_cap = skw ? in.reg_cap_skew : in.reg_cap;
-  const unsigned C = ov.C, R = NB / (8 * C), parts = 8 * C;
-  const uint64_t cap = bcap / T, scap = cap / kResShards;
-  const uint64_t seed = level_seed(0);
-  // kOv: the residue class r (hash blocks r, r + 8, ...) that runs on this block's XCD, from
-  // the XCDs the first eight hash blocks publish at their start
-  unsigned x_me = 0;
-  if (kOv) {
-    if (tid < 64) {
-      const unsigned me = xcc_id();
-      unsigned hx = kPcntOpen;
-      uint64_t m = 0;
-      for (unsigned spin = 0; spin < kOvSpin; ++spin) {
-        if (lane < 8) hx = __hip_atomic_load(const_cast<unsigned*>(ov.hxcc) + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        m = __ballot(lane < 8 && hx == me);
-        if (m) break;
-        __builtin_amdgcn_s_sleep(8);
-      }
-      if (lane == 0) s_item = m ? (unsigned)__builtin_ctzll(m) : ~0u;
-    }
-    __syncthreads();
-    x_me = s_item;
-    if (x_me >= 8) return;  // no class found: the follow-up takes every part
-    __syncthreads();
-  }
-  if (tid == 0) s_over = 0;
-  for (unsigned t = tid; t < (unsigned)kT; t += kDT) cnt[t] = 0;
-  __syncthreads();
-  bool geo = false;
-  for (;;) {
-    unsigned sidx, part;
-    if (kOv) {
-      if (tid == 0) {
-        unsigned it = ~0u;
-        if (__hip_atomic_load(&st->h0_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < NB)
-          it = (unsigned)atomicAdd(&st->ov_ticket[x_me], 1ull);
-        s_item = it;
-      }
-      __syncthreads();
-      const unsigned it = s_item;
-      if (it >= C * in.S) break;
-      sidx = it % in.S;
-      part = x_me * C + it / in.S;
-    } else {
-      sidx = blockIdx.x / parts;
-      part = blockIdx.x % parts;
-      if (ov.done && ov.done[(uint64_t)part * in.S + sidx]) break;
-    }
-    const unsigned x = part / C, c = part % C;
-    const uint64_t t0 = (uint64_t)sidx * tps;
-    if (t0 >= T) {
-      if (kOv) continue;
-      break;
-    }
-    const unsigned tn = (unsigned)min<uint64_t>(tps, T - t0);
-    if (tn > (unsigned)kT) {
-      geo = true;
-      break;
-    }
-    // the part's runs: lane i of wave 0 reads hash block x + 8 (c R + i)'s fill
-    if (tid < 64) {
-      const unsigned hb = x + 8 * (c * R + lane);
-      unsigned* const pp = const_cast<unsigned*>(in.pcnt) + (uint64_t)hb * in.S + sidx;
-      unsigned v = 0;
-      bool ok = true;
-      if (kOv) {
-        if (lane < R) v = __hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (unsigned spin = 0;; ++spin) {
-          const bool open = lane < R && v == kPcntOpen;
-          if (!__ballot(open)) break;
-          if (spin >= kOvSpin) {
-            ok = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(8);
-          if (open) v = __hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (ok) {  // every hash block of the part ran on this XCD
-          const unsigned me = xcc_id();
-          const unsigned hx =
-              lane < R ? __hip_atomic_load(const_cast<unsigned*>(ov.hxcc) + hb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : me;
-          if (__ballot(hx != me)) ok = false;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      } else if (lane < R) {
-        v = *pp;
-      }
-      if (!ok || lane >= R) v = 0;
-      unsigned incl = v;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned y = __shfl_up(incl, d);
-        if (lane >= (unsigned)d) incl += y;
-      }
-      rp[lane] = incl - v;
-      if (lane == 63) rp[64] = incl;
-      if (lane == 0) s_ok = ok ? 1u : 0u;
-    }
-    __syncthreads();
-    if (kOv && !s_ok) break;  // left to the follow-up launch
-    const unsigned tot = rp[64];
-    const R20* const rbase = in.sup;
-    for (unsigned r0 = 0; r0 < tot; r0 += kDT * kDU) {
-      uint4 rq[kDU];
-      uint32_t rz[kDU];
-      unsigned trk[kDU];
-      // the round's loads straight-line, all in flight together (indices clamped, not guarded)
-#pragma unroll
-      for (int u = 0; u < kDU; ++u) {
-        const unsigned j = min(r0 + (unsigned)u * kDT + tid, tot - 1);
-        unsigned a = 0, z = R;  // the run holding j: rp[a] <= j < rp[a + 1]
-        while (z - a > 1) {
-          const unsigned mid = (a + z) >> 1;
-          if (rp[mid] <= j) a = mid;
-          else z = mid;
-        }
-        const unsigned hb = x + 8 * (c * R + a);
-        const uint32_t* w = (rbase + ((uint64_t)hb * in.S + sidx) * reg_cap + (j - rp[a]))->w;
-        rq[u] = *reinterpret_cast<const uint4*>(w);  // dword-aligned 16-B load
-        rz[u] = w[4];
-      }
-#pragma unroll
-      for (int u = 0; u < kDU; ++u) {
-        trk[u] = ~0u;
-        if (r0 + (unsigned)u * kDT + tid < tot) {
-          const uint64_t k = (uint64_t)rq[u].x | ((uint64_t)rq[u].y << 32);
-          const uint64_t t = (bb_index(seed, k, words, magic) >> kRegTileMaxBits) - t0;
-          if (t < tn) trk[u] = ((unsigned)t << 13) | atomicAdd(&cnt[t], 1u);
-          else geo = true;
-        }
-      }
-      __syncthreads();
-      for (unsigned t = tid; t < tn; t += kDT) {
-        const unsigned n = cnt[t];
-        if (n) {
-          const unsigned at = atomicAdd(&tcnt[(t0 + t) * kResShards + x], n);
-          if (at + n > scap) s_over = 1;
-          cur[t] = (unsigned)((t0 + t) * cap + x * scap + at);
-          cnt[t] = 0;
-        }
-      }
-      __syncthreads();
-      if (s_over) break;
-#pragma unroll
-      for (int u = 0; u < kDU; ++u) {
-        if (trk[u] != ~0u) {
-          uint32_t* d = bucket[cur[trk[u] >> 13] + (trk[u] & 8191u)].w;
-          *reinterpret_cast<uint4*>(d) = rq[u];
-          d[4] = rz[u];
-        }
-      }
-    }
-    if (s_over) break;
-    if (kOv && tid == 0) ov.done[(uint64_t)part * in.S + sidx] = 1u;
-    if (!kOv) break;
-  }
-  if (geo) (atomicOr(&st->status, kStGeometry), atomicCAS(&st->pad0_, 0u, 6u));
   if (s_over && tid == 0) atomicOr(&st->status, kStOverflow | kStResOverflow);
 }
 
@@ -3103,16 +2834,12 @@ __device__ __forceinline__ uint64_t lb_resolve(unsigned long long* flags, uint64
 // k20: R20 records (identity positions: p = pos_base + key index, 12-B stage entries);
 // otherwise Rec records of any level whose tiles are 2^14 positions (16-B stage entries).
 // o20: the collided records leave as R20 (the next level's list is R20, BinBuffers::l20).
-// kPN (P0F, level 0 of a single-GPU build): the collided records go straight to level 1's
-// super-tile regions (NextPart: per (block, super-tile) regions of R20, the level-0 hash's
-// scheme) instead of level 1's list; level 1's size came from k_p0_count before this kernel.
-template <bool k20, bool kPN = false>
+template <bool k20>
 __global__ __launch_bounds__(kP0T) void k_tile_p0(int level, const void* __restrict__ bucket_v, uint64_t bucket_cap,
                                                   const unsigned* __restrict__ tcnt, unsigned long long* flags,
                                                   uint64_t* __restrict__ bits, Rec* __restrict__ next,
                                                   uint64_t* __restrict__ fp_out, uint64_t* __restrict__ pos_out,
-                                                  LevelState* st, uint64_t pos_base, bool o20, NextPart pn = NextPart{}) {
-  static_assert(!kPN || k20, "the next level's regions hold R20 records");
+                                                  LevelState* st, uint64_t pos_base, bool o20) {
   using PT = std::conditional_t<k20, uint32_t, uint64_t>;  // key index, or p
   __shared__ uint64_t sf[kP0Stage];
   __shared__ PT si[kP0Stage];
@@ -3121,12 +2848,7 @@ __global__ __launch_bounds__(kP0T) void k_tile_p0(int level, const void* __restr
   __shared__ unsigned s_cnt[2][kResShards];
   __shared__ unsigned long long s_t[2], s_b0, s_excl;
   __shared__ unsigned s_late;
-  __shared__ unsigned p_cur[kPN ? kMaxRanks : 1];  // kPN: this block's fill of each level-1 region
-  if (!level_active(level, st)) {
-    if constexpr (kPN)  // (the next level's scatter reads every block's fills)
-      for (unsigned q = threadIdx.x; q < pn.S; q += kP0T) pn.pcnt[(uint64_t)blockIdx.x * pn.S + q] = 0;
-    return;
-  }
+  if (!level_active(level, st)) return;
   const uint64_t N = st->out_cap;
   const bool out_on = level_out_on(st, level);
   const uint64_t words = st->words[level], magic = st->magic[level];
@@ -3174,30 +2896,6 @@ __global__ __launch_bounds__(kP0T) void k_tile_p0(int level, const void* __restr
       f_ = q->f;
       p_ = q->p;
     }
-  };
-  // kPN: level 1's geometry (sized by k_p0_level1_setup) and this block's region appends
-  uint64_t w1 = 0, m1 = 0, seed1 = 0;
-  uint32_t pmul = 0;
-  unsigned rcap = 0;
-  bool rover = false;
-  if constexpr (kPN) {
-    if (threadIdx.x < (unsigned)kMaxRanks) p_cur[threadIdx.x] = 0;  // (ordered by the barrier below)
-    w1 = st->words[level + 1];
-    m1 = st->magic[level + 1];
-    seed1 = level_seed(level + 1);
-    pmul = 0xffffffffu / pn.tps_sub + 1;  // exact for (position >> 14) < 2^18 (the hash's partition)
-    rcap = (unsigned)pn.reg_cap;
-  }
-  // a collided record into its level-1 super-tile's region of this block
-  auto put_region = [&](uint64_t kk, uint64_t ff, uint32_t ii) {
-    const uint64_t x1 = w1 >= (1ull << 19) ? bb_index_big(seed1, kk, w1, m1) : bb_index(seed1, kk, w1, m1);
-    unsigned sp = __umulhi((uint32_t)(x1 >> kRegTileMaxBits), pmul);
-    if (sp >= pn.S) sp = pn.S - 1;  // a level past its bound: the scatter flags the geometry
-    const unsigned at = atomicAdd(&p_cur[sp], 1u);
-    if (at < rcap)
-      pn.sup[((uint64_t)blockIdx.x * pn.S + sp) * rcap + at] = r20_make(kk, ff, ii);
-    else
-      rover = true;
   };
   uint64_t k[kP0R], f[kP0R];
   PT p[kP0R];
@@ -3344,13 +3042,9 @@ __global__ __launch_bounds__(kP0T) void k_tile_p0(int level, const void* __restr
           const unsigned j = (unsigned)r * kP0T + me;
           const unsigned x = LOC(r);
           const bool redo = j < nk && !((sA[x >> 5] >> (x & 31)) & 1u);
-          if constexpr (kPN) {
-            if (redo) put_region(k[r], f[r], (uint32_t)p[r]);
-          } else {
-            const uint64_t m = __ballot(redo);
-            if (redo) next_put(next, o20, o + __popcll(m & lt), k[r], f[r], pos_of(p[r]), pos_base);
-            o += __popcll(m);
-          }
+          const uint64_t m = __ballot(redo);
+          if (redo) next_put(next, o20, o + __popcll(m & lt), k[r], f[r], pos_of(p[r]), pos_base);
+          o += __popcll(m);
         }
       } else {
         #pragma unroll 1
@@ -3364,13 +3058,9 @@ __global__ __launch_bounds__(kP0T) void k_tile_p0(int level, const void* __restr
             const unsigned x = (unsigned)(bb_index(seed, jk, words, magic) - tbase);
             redo = !((sA[x >> 5] >> (x & 31)) & 1u);
           }
-          if constexpr (kPN) {
-            if (redo) put_region(jk, jf, (uint32_t)jp);
-          } else {
-            const uint64_t m = __ballot(redo);
-            if (redo) next_put(next, o20, o + __popcll(m & lt), jk, jf, pos_of(jp), pos_base);
-            o += __popcll(m);
-          }
+          const uint64_t m = __ballot(redo);
+          if (redo) next_put(next, o20, o + __popcll(m & lt), jk, jf, pos_of(jp), pos_base);
+          o += __popcll(m);
         }
       }
     }
@@ -3462,109 +3152,6 @@ __global__ __launch_bounds__(kP0T) void k_tile_p0(int level, const void* __restr
     cb = nb;
   }
   if (bad) atomicOr(&st->status, kStRank);
-  if constexpr (kPN) {  // (the tile loop ended on a barrier: every append is in p_cur)
-    __syncthreads();
-    for (unsigned q = tid; q < pn.S; q += kP0T) pn.pcnt[(uint64_t)blockIdx.x * pn.S + q] = min(p_cur[q], rcap);
-    if (rover) atomicOr(&st->status, kStResOverflow);  // a region overflowed: the build reruns
-  }
-}
-
-// ---- P0F: level 1 fed by level 0's tile kernel -------------------------------------------
-// Level 1's geometry needs its exact size, which the single-GPU build otherwise learns only
-// once level 0's tile kernel has finished; k_p0_count gets it first.  Per 2^14-position tile
-// of level 0 it marks A / C in LDS from each slot's in-tile position (a u16 the super-tile
-// scatter wrote beside the record: 2 B per key read instead of 20) and counts the settled keys,
-// popcount(A & ~C), into st->settled0; k_p0_level1_setup then sizes level 1 from N minus
-// them, and k_tile_p0<true, true> writes level 1's records straight into its super-tile regions
-// (the level-0 hash's scheme).  Level 1 then reaches 2^14-position register tiles through the
-// super-tile scatter, instead of the reservation scatter and the split kernel's sub-tile
-// scratch (40 B per record written and read back).
-constexpr int kCntT = 512;
-constexpr int kCntU = 4;  // slot positions in flight per thread
-__global__ __launch_bounds__(kCntT) void k_p0_count(const uint16_t* __restrict__ xs, const unsigned* __restrict__ tcnt,
-                                                   uint64_t bucket_cap, LevelState* st) {
-  __shared__ uint32_t sA[kP0W32], sC[kP0W32];
-  __shared__ unsigned s_fo[kResShards + 1];
-  __shared__ unsigned long long s_w[kCntT / 64];
-  if (st->status & kStStop) return;
-  const uint64_t T = st->ntiles[0];
-  if (T == 0) return;
-  const uint64_t cap = bucket_cap / T, scap = cap / kResShards;
-  const unsigned tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-  unsigned long long settled = 0;
-  for (uint64_t t = blockIdx.x; t < T; t += gridDim.x) {
-    for (unsigned w = tid; w < kP0W32; w += kCntT) {
-      sA[w] = 0;
-      sC[w] = 0;
-    }
-    if (wave == 0) {  // the tile's slot fills: exclusive prefix over lanes 0-7
-      const unsigned c = lane < (unsigned)kResShards ? tcnt[t * kResShards + lane] : 0u;
-      unsigned x = c;
-#pragma unroll
-      for (int d = 1; d < kResShards; d <<= 1) {
-        const unsigned y = __shfl_up(x, d);
-        if (lane >= (unsigned)d) x += y;
-      }
-      if (lane < (unsigned)kResShards) s_fo[lane] = x - c;
-      if (lane == (unsigned)kResShards - 1) s_fo[kResShards] = x;
-    }
-    __syncthreads();
-    unsigned fo[kResShards + 1];
-#pragma unroll
-    for (int q = 0; q <= kResShards; ++q) fo[q] = s_fo[q];
-    const unsigned nrec = fo[kResShards];
-    for (unsigned i0 = 0; i0 < nrec; i0 += kCntT * kCntU) {
-      unsigned x[kCntU];
-#pragma unroll
-      for (int u = 0; u < kCntU; ++u) {  // straight-line, clamped: all loads in flight together
-        const unsigned i = min(i0 + u * kCntT + tid, nrec - 1);
-        unsigned sh = 0;
-#pragma unroll
-        for (int q = 1; q < kResShards; ++q) sh += i >= fo[q] ? 1u : 0u;
-        unsigned b = fo[0];
-#pragma unroll
-        for (int q = 1; q < kResShards; ++q)
-          if (sh == (unsigned)q) b = fo[q];
-        x[u] = xs[t * cap + (uint64_t)sh * scap + (i - b)];
-      }
-#pragma unroll
-      for (int u = 0; u < kCntU; ++u) {
-        if (i0 + u * kCntT + tid >= nrec) continue;
-        const uint32_t bit = 1u << (x[u] & 31);
-        const uint32_t old = atomicOr(&sA[x[u] >> 5], bit);
-        if (old & bit) atomicOr(&sC[x[u] >> 5], bit);
-      }
-    }
-    __syncthreads();
-    for (unsigned w = tid; w < kP0W32; w += kCntT) settled += (unsigned)__popc(sA[w] & ~sC[w]);
-    __syncthreads();
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) settled += __shfl_xor(settled, d);
-  if (lane == 0) s_w[wave] = settled;
-  __syncthreads();
-  if (tid == 0) {
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int w = 0; w < kCntT / 64; ++w) sum += s_w[w];
-    if (sum) atomicAdd(&st->settled0, sum);
-  }
-}
-
-// Level 1's words, Barrett reciprocal and word offsets from its exact size (n[0] minus level 0's
-// settled keys), as k_scatter_res's level setup would write them; n[1] itself is still counted
-// by level 0's tile kernel (the same value).
-__global__ void k_p0_level1_setup(LevelState* st, uint64_t cap_words) {
-  if (threadIdx.x != 0 || blockIdx.x != 0 || (st->status & kStStop)) return;
-  const uint64_t n1 = st->n[0] - st->settled0;
-  const uint64_t w = level_words(n1);
-  st->words[1] = w;
-  st->magic[1] = level_magic(w);
-  st->woff[1] = st->woff[0] + st->words[0];
-  st->woff[2] = st->woff[1] + w;
-  st->nlevels = 1;
-  if (st->woff[2] > cap_words) atomicOr(&st->status, kStOverflow);
-  if (n1 <= kGate) (atomicOr(&st->status, kStGeometry), atomicCAS(&st->pad0_, 0u, 6u));  // (never at P0 sizes)
 }
 
 // ------------------------------------------------------------ mid-size levels --------
@@ -3653,8 +3240,7 @@ __global__ __launch_bounds__(kMidT) void k_mid_levels(int L0, int L1, Rec* list0
   __shared__ int s_go, s_ok;
 
   const unsigned g = blockIdx.x, G = gridDim.x;
-  // zeroed by k_init_state: one launch of each form per build attempt
-  unsigned* bar = kG == kMidG ? &st->mid_bar : &st->mid_bar2;
+  unsigned* bar = &st->mid_bar;  // zeroed by k_init_state: one launch per build attempt
   unsigned* xc = mid + Cfg::kXc;  // [owner][sender] segment counts
   unsigned long long* tot = reinterpret_cast<unsigned long long*>(mid + Cfg::kTot);
   const uint64_t N = st->out_cap;
@@ -4341,43 +3927,18 @@ size_t tile_lds_bytes(unsigned tb) {
 
 uint64_t split_scratch_records() { return split_scratch_recs(); }
 
-// The skewed-length level-0 hash (a no-op launch unless st->skew).  A/B knobs:
-// b.skew_cfg (S3IMPH_SKEW_CFG at context creation) selects the block / group shape: 2
-// (default) one 768-thread block per CU with 5120-key groups, 1 one 1024-thread block with
-// 4096-key groups (C5 1.65 vs 1.61 ms), 0 two 512-thread blocks per CU with 2048-key groups
-// (1.75 ms), 3 (partition form only, else 2) two 512-thread blocks per CU with 5120-key groups
-// and no result arrays; S3IMPH_SKEW_ORDER=0 alternates the longest and the shortest batch instead of
-// longest first.
+// The skewed-length level-0 hash (a no-op launch unless st->skew): one 768-thread block per CU
+// with 5120-key groups, kP0SkewBlocks blocks (C5: 1.61 ms against 1.65 for one 1024-thread block
+// with 4096-key groups and 1.75 for two 512-thread blocks per CU with 2048-key groups).
 void launch_hash_skew(const uint8_t* blob, const uint64_t* offsets, uint64_t n, const BinBuffers& b, LevelGeom g,
                       unsigned long long* prof, hipStream_t s, const P0Part& pt = P0Part{}) {
-  const int cfg = b.skew_cfg;
-  static const int order = [] {  // 1: longest first; 0: alternating longest / shortest
-    const char* e = dev_env("S3IMPH_SKEW_ORDER");
-    return e ? std::atoi(e) : 1;
-  }();
-  if (cfg == 3 && pt.sup)  // the partition form, two blocks per CU (p0_skew_blocks sized its regions)
-    k_hash_skew<512, 5120, false><<<512, 512, sk_lds_bytes<512, 5120, false>(), s>>>(
-        blob, offsets, n, b.kh, b.fp, b.flags, b.sflags, b.st, g.tb, g.chunk, b.tcnt, prof, order, pt);
-  else if (cfg == 1)
-    k_hash_skew<1024, 4096><<<256, 1024, sk_lds_bytes<1024, 4096>(), s>>>(
-        blob, offsets, n, b.kh, b.fp, b.flags, b.sflags, b.st, g.tb, g.chunk, b.tcnt, prof, order, pt);
-  else if (cfg == 2 || cfg == 3)
-    k_hash_skew<768, 5120><<<256, 768, sk_lds_bytes<768, 5120>(), s>>>(
-        blob, offsets, n, b.kh, b.fp, b.flags, b.sflags, b.st, g.tb, g.chunk, b.tcnt, prof, order, pt);
-  else
-    k_hash_skew<512, 2048><<<512, 512, sk_lds_bytes<512, 2048>(), s>>>(
-        blob, offsets, n, b.kh, b.fp, b.flags, b.sflags, b.st, g.tb, g.chunk, b.tcnt, prof, order, pt);
+  k_hash_skew<768, 5120><<<kP0SkewBlocks, 768, sk_lds_bytes<768, 5120>(), s>>>(
+      blob, offsets, n, b.kh, b.fp, b.flags, b.sflags, b.st, g.tb, g.chunk, b.tcnt, prof, pt);
 }
 
 void binned_set_lds_limits() {
-  (void)hipFuncSetAttribute((const void*)k_hash_skew<1024, 4096>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sk_lds_bytes<1024, 4096>());
-  (void)hipFuncSetAttribute((const void*)k_hash_skew<512, 2048>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sk_lds_bytes<512, 2048>());
   (void)hipFuncSetAttribute((const void*)k_hash_skew<768, 5120>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)sk_lds_bytes<768, 5120>());
-  (void)hipFuncSetAttribute((const void*)k_hash_skew<512, 5120, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sk_lds_bytes<512, 5120, false>());
   (void)hipFuncSetAttribute((const void*)k_tile<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)std::max(tile_lds_bytes(kTileMaxBits), tile_lds_bytes(kCacheBits)));
   (void)hipFuncSetAttribute((const void*)k_tile_reg<512, 20, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -4392,20 +3953,8 @@ void binned_set_lds_limits() {
 template <bool PT>
 void launch_hash_pieces(const uint8_t* blob, const uint64_t* offsets, uint64_t n, const BinBuffers& b, LevelGeom g,
                         unsigned long long* prof, const P0Part& pt, hipStream_t s) {
-  // A/B knob S3IMPH_H0_PAD: dynamic LDS bytes added to each block (3072: three blocks per CU
-  // instead of four, leaving the LDS of one co-resident 256-thread super-tile scatter block)
-  // The overlapped scatter (pt.hxcc) takes the fourth slot: 3072 B by default (S3IMPH_OV_PAD)
-  static const unsigned pad = [] {
-    const char* e = dev_env("S3IMPH_H0_PAD");
-    return e ? (unsigned)std::atoi(e) : 0u;
-  }();
-  static const unsigned ov_pad = [] {
-    const char* e = dev_env("S3IMPH_OV_PAD");
-    return e ? (unsigned)std::atoi(e) : 3072u;
-  }();
-  const unsigned pd = PT && pt.hxcc ? ov_pad : pad;
   auto go = [&](unsigned b0, unsigned nb) {
-    k_hash0_pair<kH0T, kH0B, true, false, PT><<<nb, kH0T, pd, s>>>(blob, offsets, n, b.kh, b.fp, b.flags, b.sflags, b.st,
+    k_hash0_pair<kH0T, kH0B, true, false, PT><<<nb, kH0T, 0, s>>>(blob, offsets, n, b.kh, b.fp, b.flags, b.sflags, b.st,
                                                                  g.tb, g.chunk, b.tcnt, prof, Route0{}, pt, b0,
                                                                  (unsigned)kH0Grid);
   };
@@ -4549,35 +4098,28 @@ void launch_binned_scatter_res(int level, const BinBuffers& b, LevelGeom g, int 
   // LDS count / start / cursor arrays sized to the level's tiles (tmax: the host's bound;
   // a level past it flags kStGeometry and reruns), the freed LDS taken by longer rounds
   // (more records per tile per round: longer runs, fewer reservation atomics per record).
-  // b.scat_cfg (S3IMPH_SCAT_CFG at context creation; A/B knob and test hook): 0 the 4096-tile /
-  // 4096-record kernel for every level; 1 tiles by tmax, 4096-record rounds; 2 (default) tiles
-  // by tmax, longer rounds.
-  const int cfg = b.scat_cfg;
-  const int kt = cfg == 0 || tmax == 0 || tmax > 2048 ? 4096 : tmax > 1024 ? 2048 : 1024;
+  // b.scat_cfg == 0 (S3IMPH_SCAT_CFG=0 at context creation; test hook): the 4096-tile /
+  // 4096-record kernel for every level.
+  const int kt = b.scat_cfg == 0 || tmax == 0 || tmax > 2048 ? 4096 : tmax > 1024 ? 2048 : 1024;
   // (longer rounds with 2048 counters too: they spill 6-8 VGPRs against 0-4, yet measured
   // faster on C2's level 0 than 4096-record rounds there, 0.144-0.149 vs 0.152-0.154 ms)
-  auto pick = [&](auto r4096, auto r_long) {
-    return cfg == 2 ? r_long : r4096;
-  };
   using KFn = decltype(&k_scatter_res<kSubRound, kLdsTiles, 0>);
   KFn kern;
   const bool l20 = !l0 && b.list20(level);  // an R20 list (kSrc 4) into R20 slots
   if (l20) {
-    kern = kt == 1024   ? pick(k_scatter_res<4096, 1024, 4, true>, k_scatter_res<6144, 1024, 4, true>)
-           : kt == 2048 ? pick(k_scatter_res<4096, 2048, 4, true>, k_scatter_res<6144, 2048, 4, true>)
+    kern = kt == 1024   ? k_scatter_res<6144, 1024, 4, true>
+           : kt == 2048 ? k_scatter_res<6144, 2048, 4, true>
                         : k_scatter_res<kSubRound, kLdsTiles, 4, true>;
   } else if (kt == 1024) {
-    kern = !l0    ? (b.padded ? pick(k_scatter_res<4096, 1024, 3>, k_scatter_res<5120, 1024, 3>)
-                              : pick(k_scatter_res<4096, 1024, 0>, k_scatter_res<5120, 1024, 0>))
-           : b.pos ? pick(k_scatter_res<4096, 1024, 1>, k_scatter_res<5120, 1024, 1>)
-           : p20   ? pick(k_scatter_res<4096, 1024, 2, true>, k_scatter_res<6144, 1024, 2, true>)
-                   : pick(k_scatter_res<4096, 1024, 2>, k_scatter_res<5120, 1024, 2>);
+    kern = !l0    ? (b.padded ? k_scatter_res<5120, 1024, 3> : k_scatter_res<5120, 1024, 0>)
+           : b.pos ? k_scatter_res<5120, 1024, 1>
+           : p20   ? k_scatter_res<6144, 1024, 2, true>
+                   : k_scatter_res<5120, 1024, 2>;
   } else if (kt == 2048) {
-    kern = !l0    ? (b.padded ? pick(k_scatter_res<4096, 2048, 3>, k_scatter_res<5120, 2048, 3>)
-                              : pick(k_scatter_res<4096, 2048, 0>, k_scatter_res<5120, 2048, 0>))
-           : b.pos ? pick(k_scatter_res<4096, 2048, 1>, k_scatter_res<5120, 2048, 1>)
-           : p20   ? pick(k_scatter_res<4096, 2048, 2, true>, k_scatter_res<6144, 2048, 2, true>)
-                   : pick(k_scatter_res<4096, 2048, 2>, k_scatter_res<5120, 2048, 2>);
+    kern = !l0    ? (b.padded ? k_scatter_res<5120, 2048, 3> : k_scatter_res<5120, 2048, 0>)
+           : b.pos ? k_scatter_res<5120, 2048, 1>
+           : p20   ? k_scatter_res<6144, 2048, 2, true>
+                   : k_scatter_res<5120, 2048, 2>;
   } else {
     kern = !l0    ? (b.padded ? k_scatter_res<kSubRound, kLdsTiles, 3> : k_scatter_res<kSubRound, kLdsTiles, 0>)
            : b.pos ? k_scatter_res<kSubRound, kLdsTiles, 1>
@@ -4595,16 +4137,10 @@ static unsigned mid_seq() {
   return (q.fetch_add(1, std::memory_order_relaxed) + 1) & ((1u << 26) - 1);
 }
 
-void launch_binned_mid(int L0, int L1, const BinBuffers& b, hipStream_t s, bool big) {
-  if (big)
-    k_mid_levels<kMidGBig><<<kMidGBig, kMidT, 0, s>>>(L0, L1, b.list[0], b.list[1], b.bits, b.cap_words, b.fp_out,
-                                                     b.pos_out, b.st, b.mid,
-                                                     reinterpret_cast<Rec*>(b.mid + MidCfg<kMidGBig>::kXb),
-                                                     b.tile_prof, mid_seq());
-  else
-    k_mid_levels<kMidG><<<kMidG, kMidT, 0, s>>>(L0, L1, b.list[0], b.list[1], b.bits, b.cap_words, b.fp_out,
-                                                b.pos_out, b.st, b.mid, reinterpret_cast<Rec*>(b.mid + MidCfg<kMidG>::kXb),
-                                                b.tile_prof, mid_seq());
+void launch_binned_mid(int L0, int L1, const BinBuffers& b, hipStream_t s) {
+  k_mid_levels<kMidG><<<kMidG, kMidT, 0, s>>>(L0, L1, b.list[0], b.list[1], b.bits, b.cap_words, b.fp_out, b.pos_out,
+                                              b.st, b.mid, reinterpret_cast<Rec*>(b.mid + MidCfg<kMidG>::kXb),
+                                              b.tile_prof, mid_seq());
 }
 
 void launch_binned_tail(int first_level, int big_launched, const BinBuffers& b, hipStream_t s) {
@@ -4639,7 +4175,6 @@ uint64_t p0_region_cap(uint64_t n, unsigned S, unsigned blocks) {
   const double per = (double)((n + blocks - 1) / blocks), mean = per / S;
   return (uint64_t)(mean + 10.0 * std::sqrt(mean) + 32.0);
 }
-unsigned p0_skew_blocks(int skew_cfg) { return skew_cfg == 0 || skew_cfg == 3 ? 512u : 256u; }  // launch_hash_skew's grid
 
 // P0 level 0's hash and first partition: fused (k_hash0_pair<..., PT>) for an aligned blob
 // of up to kMaxRanks super-tiles, with k_hash_skew + the partition pass standing by for a
@@ -4648,11 +4183,11 @@ void launch_p0_hash(const uint8_t* blob, const uint64_t* offsets, uint64_t n, co
                     const P0Bufs& p, hipStream_t s) {
   if (p0_fused(blob, p)) {
     unsigned long long* prof = b.tile_prof ? b.tile_prof + (uint64_t)(kMaxLevels - 3) * kMaxTiles * 8 : nullptr;
-    const P0Part pt{p.sup, p.reg_cap, p.pcnt, p.tps_sub(), p.S, p.hxcc};
+    const P0Part pt{p.sup, p.reg_cap, p.pcnt, p.tps_sub(), p.S};
     launch_hash_pieces<true>(blob, offsets, n, b, g, prof, pt, s);
     if (b.feed) b.feed->ensure(n);
     // a skewed set: k_hash_skew's groups partition the same way, into regions of its own
-    // (fewer, larger: p0_skew_blocks blocks, reg_cap_skew records each)
+    // (fewer, larger: kP0SkewBlocks blocks, reg_cap_skew records each)
     const P0Part pts{p.sup, p.reg_cap_skew, p.pcnt, p.tps_sub(), p.S};
     launch_hash_skew(blob, offsets, n, b, g, prof, s, pts);
     return;
@@ -4666,7 +4201,7 @@ __global__ void k_set_status(LevelState* st, unsigned f) {
 }
 
 void launch_p0_scatter(const BinBuffers& b, const P0Bufs& p, bool fused, hipStream_t s, int level) {
-  const P0In in{p.sup, p.reg_cap, p.pcnt, p.nb ? p.nb : (unsigned)kH0Grid, p.S, p0_skew_blocks(b.skew_cfg),
+  const P0In in{p.sup, p.reg_cap, p.pcnt, p.nb ? p.nb : (unsigned)kH0Grid, p.S, kP0SkewBlocks,
                 p.reg_cap_skew, p.sup_cap, p.scnt, fused};
   // blocks per super-tile: a multiple of kResShards, so every shard slot of a tile takes the
   // records of the same number of blocks (9 blocks put 2/9 of a super-tile's records on one
@@ -4674,52 +4209,9 @@ void launch_p0_scatter(const BinBuffers& b, const P0Bufs& p, bool fused, hipStre
   // More than 32 super-tiles (C3: 64 of ~191 tiles) take the one-block form too: 8 blocks of
   // 1024 threads per super-tile, 512 blocks dispatched in two waves over the 256 CUs, 6144-record
   // rounds of ~32 records per tile (C3 scatter0_p0 1.22 -> 1.09-1.11 ms, the fused partition's
-  // hash +0.09; step -0.05 ms over two same-box A/Bs).  S3IMPH_P0_BIG=0: the two-block form below.
-  static const bool big = [] {
-    const char* e = dev_env("S3IMPH_P0_BIG");
-    return !(e && std::atoi(e) == 0);
-  }();
-  if (p.S > kP0OneBlockS && !big) {
-    // more than 32 super-tiles: 8 blocks of 512 threads each (two per CU), 3072-record rounds
-    // (2560 with 1024-tile counters, so two blocks' LDS fit a CU): shorter rounds than the
-    // one-block form's 5120, but as many records per tile and round at S = 64 (tps ~ 191 vs
-    // 382), and one block's count / scan / stage phases run beside the other's loads and stores
-    constexpr unsigned bps = kResShards;
-    if (p.tps <= 256)
-      k_scatter_p0<3072, 256, 512><<<p.S * bps, 512, 0, s>>>(in, bps, p.tps, p.bucket, p.bucket_cap, p.tcnt, p.flags,
-                                                             b.st, b.tile_prof, kRegTileMaxBits, nullptr, level);
-    else if (p.tps <= 512)
-      k_scatter_p0<3072, 512, 512><<<p.S * bps, 512, 0, s>>>(in, bps, p.tps, p.bucket, p.bucket_cap, p.tcnt, p.flags,
-                                                             b.st, b.tile_prof, kRegTileMaxBits, nullptr, level);
-    else
-      k_scatter_p0<2560, 1024, 512><<<p.S * bps, 512, 0, s>>>(in, bps, p.tps, p.bucket, p.bucket_cap, p.tcnt, p.flags,
-                                                              b.st, b.tile_prof, kRegTileMaxBits, nullptr, level);
-    return;
-  }
-  static const unsigned bps_knob = [] {  // A/B knob S3IMPH_P0_BPS: blocks per super-tile (a multiple of 8)
-    const char* e = dev_env("S3IMPH_P0_BPS");
-    const unsigned v = e ? (unsigned)std::atoi(e) : 0u;
-    return v / kResShards * kResShards;
-  }();
-  const unsigned bps = bps_knob ? bps_knob : std::max(1u, kP0ScatterBlocks / p.S / kResShards) * kResShards;
-  // A/B knob S3IMPH_P0_SMALL: 256-thread blocks with 1280-record rounds (~33 KB of LDS, less than
-  // three padded hash blocks leave on a CU), as many blocks per super-tile as keep a block's runs
-  // <= 256
-  static const bool small = [] {
-    const char* e = dev_env("S3IMPH_P0_SMALL");
-    return e && std::atoi(e) != 0;
-  }();
-  if (small && !p.x && p.tps <= 512) {
-    const unsigned nb = fused ? in.NB : 0u;
-    const unsigned bsm = std::max(bps, ((nb + 255) / 256 + kResShards - 1) / kResShards * kResShards);
-    if (p.tps <= 256)
-      k_scatter_p0<1280, 256, 256><<<p.S * bsm, 256, 0, s>>>(in, bsm, p.tps, p.bucket, p.bucket_cap, p.tcnt, p.flags,
-                                                             b.st, b.tile_prof, kRegTileMaxBits, nullptr, level);
-    else
-      k_scatter_p0<1280, 512, 256><<<p.S * bsm, 256, 0, s>>>(in, bsm, p.tps, p.bucket, p.bucket_cap, p.tcnt, p.flags,
-                                                             b.st, b.tile_prof, kRegTileMaxBits, nullptr, level);
-    return;
-  }
+  // hash +0.09; step -0.05 ms over two same-box A/Bs, against 8 blocks of 512 threads per
+  // super-tile, two per CU, with 3072-record rounds).
+  const unsigned bps = std::max(1u, kP0ScatterBlocks / p.S / kResShards) * kResShards;
   if (p.x) {
     // the bitmap decomposition: tiles of 2^p.tb positions, each record's in-tile position to
     // p.x as well; its levels have at most kBmMaxTiles tiles in <= 64 super-tiles of <= 1024
@@ -4747,41 +4239,9 @@ void launch_p0_scatter(const BinBuffers& b, const P0Bufs& p, bool fused, hipStre
                                                         b.tile_prof, kRegTileMaxBits, nullptr, level);
 }
 
-// The super-tile scatter's direct form (k_scatter_p0d): ov, the persistent launch beside the
-// level-0 hash (one block per CU); otherwise one block per (super-tile, part), skipping the
-// parts an overlapped launch finished (p.ov_done, or none).
-void launch_p0_scatter_direct(const BinBuffers& b, const P0Bufs& p, bool ov, hipStream_t s) {
-  const P0In in{p.sup, p.reg_cap, p.pcnt, (unsigned)kH0Grid, p.S, p0_skew_blocks(b.skew_cfg),
-                p.reg_cap_skew, p.sup_cap, p.scnt, true};
-  const P0Ov o{p.hxcc, p.ov_done, kP0OvChunks};
-  const unsigned grid = ov ? 256u : p.S * 8u * kP0OvChunks;
-#define S3_P0D(KT)                                                                                                  \
-  (ov ? k_scatter_p0d<KT, true> : k_scatter_p0d<KT, false>)<<<grid, kDT, 0, s>>>(in, p.tps, p.bucket, p.bucket_cap,  \
-                                                                                   p.tcnt, p.flags, b.st, o)
-  if (p.tps <= 256) S3_P0D(256);
-  else if (p.tps <= 512) S3_P0D(512);
-  else S3_P0D(1024);
-#undef S3_P0D
-}
-
 void launch_p0_tile(const BinBuffers& b, const P0Bufs& p, hipStream_t s) {
   k_tile_p0<true><<<256, kP0T, 0, s>>>(0, p.bucket, p.bucket_cap, p.tcnt, p.flags, b.bits, b.list[0], b.fp_out,
                                        b.pos_out, b.st, b.pos_base, b.list20(1));
-}
-
-void launch_p0_count(const BinBuffers& b, const P0Bufs& p, hipStream_t s) {
-  k_p0_count<<<1024, kCntT, 0, s>>>(p.x, p.tcnt, p.bucket_cap, b.st);
-  k_p0_level1_setup<<<1, 64, 0, s>>>(b.st, b.cap_words);
-}
-
-void launch_p0_tile_fed(const BinBuffers& b, const P0Bufs& p, const NextPart& np, hipStream_t s) {
-  k_tile_p0<true, true><<<kP0FedGrid, kP0T, 0, s>>>(0, p.bucket, p.bucket_cap, p.tcnt, p.flags, b.bits, nullptr,
-                                                    b.fp_out, b.pos_out, b.st, b.pos_base, true, np);
-}
-
-void launch_p0_tile_level(int level, const BinBuffers& b, const P0Bufs& p, hipStream_t s) {
-  k_tile_p0<true><<<256, kP0T, 0, s>>>(level, p.bucket, p.bucket_cap, p.tcnt, p.flags, b.bits, b.list[level & 1],
-                                       b.fp_out, b.pos_out, b.st, b.pos_base, b.list20(level + 1));
 }
 
 }  // namespace s3imph

@@ -103,7 +103,6 @@ void free_bm_workspace(DistState& d);
 
 void free_workspace(s3imph_ctx* c) {
   dfree(c->mid);
-  c->mid_cap = 0;
   dfree(c->split);
   dfree(c->kh); dfree(c->fp); dfree(c->bits); dfree(c->rank_base);
   c->rank_base_cap = 0;
@@ -112,7 +111,6 @@ void free_workspace(s3imph_ctx* c) {
   dfree(c->bucket); dfree(c->list[0]); dfree(c->list[1]);
   dfree(c->tcnt);
   dfree(c->p0_tcnt); dfree(c->p0_flags); dfree(c->p0_scnt); dfree(c->p0_pcnt); dfree(c->p0_sup); dfree(c->p0_x);
-  dfree(c->p0_ov);
   c->p0_x_cap = 0;
   c->p0_tiles = 0;
   c->p0_sup_cap = 0;
@@ -278,7 +276,6 @@ void fault_dup_record(s3imph_ctx* c, Rec* list, hipStream_t s, bool r20 = false)
     HIPCHECK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(list) + sz, list, sz, hipMemcpyDeviceToDevice, s));
 }
 
-int mid_big_mode();
 BinBuffers make_bufs(s3imph_ctx* c, const uint64_t* pos, uint64_t* fp_out, uint64_t* pos_out, hipStream_t s) {
   BinBuffers b{};
   b.feed = c->feed;
@@ -304,24 +301,13 @@ BinBuffers make_bufs(s3imph_ctx* c, const uint64_t* pos, uint64_t* fp_out, uint6
     HIPCHECK(hipMemsetAsync(c->tile_prof, 0, nprof * sizeof(unsigned long long), s));
     b.tile_prof = c->tile_prof;
   }
-  {  // the 256-workgroup mid levels' scratch (201 MB) for sets that may have a level of 440k-1.75M keys
-    const uint64_t need = c->cap_keys >= kMidBigMinKeys && mid_big_mode() != 0
-                              ? std::max<uint64_t>(kMidScratchU32, MidCfg<kMidGBig>::kScratchU32)
-                              : kMidScratchU32;
-    if (!c->mid || c->mid_cap < need) {
-      c->mid_cap = 0;
-      dfree(c->mid);
-      dalloc(c->mid, need);
-      c->mid_cap = need;
-    }
-  }
+  if (!c->mid) dalloc(c->mid, kMidScratchU32);
   b.mid = c->mid;
   // 2^15 / 2^16-position tiles appear once a level has more than 2^14 x 4096 positions
   if (!c->split && c->cap_keys > (kMaxTiles << kRegTileMaxBits) / 2) dalloc(c->split, split_scratch_records());
   b.split = c->split;
   b.scat_cfg = c->scat_cfg;
   b.pipe_tiles = c->p0 != 0;
-  b.skew_cfg = c->skew_cfg;
   b.bits = c->bits;
   b.cap_words = c->cap_words;
   b.fp_out = fp_out;
@@ -354,19 +340,6 @@ Grids level_grids(uint64_t nk, uint64_t size, LevelGeom g) {
 // Shards follow the XCDs (blockIdx % 8): 16 shards measured far slower (C3 level-0
 // scatter 1.60 -> 2.87 ms), the runs of an XCD's blocks no longer meet in its L2.  An overflow is caught on the device and
 // the build reruns on the counted path.
-// Mid levels over every CU (k_mid_levels<kMidGBig>) for levels of 440k-1.75M keys (A/B knob
-// S3IMPH_MID_BIG: 0 off (default), 1 those levels only, 2 every level down to the tail).
-// Bit-exact, and slower than the binned kernels it replaces (C2 levels 0.280 -> 0.320 / 0.354
-// ms, C5 0.54 -> 0.58 / 0.61): a level's barrier and all-gather over 256
-// workgroups cost more than a level's two launches.
-int mid_big_mode() {
-  static const int v = [] {
-    const char* e = dev_env("S3IMPH_MID_BIG");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-
 bool res_fits(const s3imph_ctx* c, uint64_t nb, uint64_t size, uint64_t T = 0) {
   if (nb * (nb > kResSmallKeys ? c->res_fill : 4) <= c->bucket_cap) return true;
   if (T == 0) {
@@ -387,12 +360,7 @@ unsigned choose_split_ts(uint64_t size, bool exact) {
   const double est = exact ? (double)size : (double)size / 1.1;
   unsigned best = 0;
   double best_cost = 0;
-  // A/B knob S3IMPH_TS_MAX: the largest ts tried (smaller sub-tile scratch per workgroup)
-  static const unsigned ts_max = [] {
-    const char* e = dev_env("S3IMPH_TS_MAX");
-    return e ? std::max(2u, std::min((unsigned)std::atoi(e), 1u << (kSplitMaxBits - 14))) : 1u << (kSplitMaxBits - 14);
-  }();
-  for (unsigned ts = 2; ts <= ts_max; ++ts) {
+  for (unsigned ts = 2; ts <= 1u << (kSplitMaxBits - 14); ++ts) {
     const double T = est / (double)((uint64_t)ts << 14);
     if (T > (double)kSplitTargetTiles) continue;
     const double rounds = std::ceil(T / ((exact ? 1.0 : 0.95) * kSplitGridHost));
@@ -455,7 +423,6 @@ struct LevelsPlan {
     ListPlan pl;
   };
   std::vector<Lv> lv;
-  int midB0 = -1, midB1 = -1;  // levels over kMidGBig workgroups (k_mid_levels<kMidGBig>), before mid0..mid1
   int mid0 = -1, mid1 = -1;
   int launched;  // the last big level launched (L0 - 1 if none)
 };
@@ -471,27 +438,6 @@ LevelsPlan plan_levels_from(s3imph_ctx* c, const BinBuffers& b, int L0, uint64_t
     // kStTailOverflow and rerun conservatively).
     const double pred = (double)n0 * std::pow(q, L - L0);
     if (!conservative && pred * kTailMargin < (double)kTailKeys) break;
-    // a level of 440k-1.75M keys (bound: 2 % + 6 sigma, as the binned geometry's): the
-    // 256-workgroup mid kernel, with the levels after it that the small one would not take
-    // (mode 2: every level down to the tail)
-    // (its grid barrier needs all 256 CUs at once: not while other ranks share the GPU)
-    const int mb = !c->dist || (c->d.comm && c->d.comm->owns_gpu()) ? mid_big_mode() : 0;
-    if (!conservative && mb != 0 && P.midB0 < 0 && pred * kMidMargin > (double)kMidMaxKeys &&
-        c->mid_cap >= MidCfg<kMidGBig>::kScratchU32 &&
-        pred * 1.02 + 6.0 * std::sqrt(pred) + 1024.0 <= (double)kMidMaxKeysBig) {
-      int L1 = L;
-      while (L1 + 1 <= big && L1 + 1 < kMaxLevels - 1) {
-        const double pn = pred * std::pow(q, L1 + 1 - L);
-        if (pn * kTailMargin < (double)kTailKeys) break;
-        if (mb == 1 && pn * kMidMargin <= (double)kMidMaxKeys) break;
-        ++L1;
-      }
-      P.midB0 = L;
-      P.midB1 = L1;
-      P.launched = L1;
-      L = L1;
-      continue;
-    }
     if (!conservative && pred * kMidMargin <= (double)kMidMaxKeys) {
       // this level and the rest above the tail: one persistent launch
       int L1 = L;
@@ -506,7 +452,7 @@ LevelsPlan plan_levels_from(s3imph_ctx* c, const BinBuffers& b, int L0, uint64_t
     const uint64_t nb = conservative ? n0 : (uint64_t)(pred * 1.1) + 4096;
     // geometry from a tight bound on the level's size (level sizes concentrate: sigma ~ sqrt(n));
     // a level past it flags kStGeometry and the build reruns conservatively
-    const bool tight = !conservative && !c->loose_geom;
+    const bool tight = !conservative;
     const uint64_t nsz = tight ? (uint64_t)(pred * 1.02 + 6.0 * std::sqrt(pred)) + 1024 : nb;
     const uint64_t size = 64 * level_words(nsz);
     P.lv.push_back({L, nb, size, tight,
@@ -538,7 +484,6 @@ int run_levels(s3imph_ctx* c, const BinBuffers& b, const LevelsPlan& P, int L0, 
     const LevelGeom g = v.pl.g;
     enqueue_list_level(c, b, v.L, v.nb, v.size, false, &g, s, v.tight);
   }
-  if (P.midB0 >= 0) launch_binned_mid(P.midB0, P.midB1, b, s, true);
   if (P.mid0 >= 0) launch_binned_mid(P.mid0, P.mid1, b, s);
   ev_mark(c, s, "levels");
   launch_binned_tail(L0, P.launched, b, s);
@@ -608,7 +553,7 @@ uint64_t p0_super_tiles(uint64_t T, uint64_t target) {
 // stands in for it), the tiles' slots in the bucket, both as R20.
 // The geometry alone (no allocation, no memset): what p0_bufs takes for the same arguments,
 // and the R20 records c->p0_sup must hold for it
-P0Bufs p0_geom(const s3imph_ctx* c, uint64_t n, uint64_t n_geom, unsigned tb, uint64_t* need) {
+P0Bufs p0_geom(uint64_t n, uint64_t n_geom, unsigned tb, uint64_t* need) {
   const uint64_t T = tiles_of(level_words(n_geom), tb, 0);
   P0Bufs p;
   p.tb = tb;
@@ -619,10 +564,9 @@ P0Bufs p0_geom(const s3imph_ctx* c, uint64_t n, uint64_t n_geom, unsigned tb, ui
   p.S = (unsigned)p0_super_tiles(T, target);
   p.tps = (unsigned)((T + p.S - 1) / p.S);
   p.reg_cap = p0_region_cap(n, p.S, kH0GridHost);
-  const unsigned nbs = p0_skew_blocks(c->skew_cfg);
-  p.reg_cap_skew = p0_region_cap(n, p.S, nbs);
+  p.reg_cap_skew = p0_region_cap(n, p.S, kP0SkewBlocks);
   *need = std::max<uint64_t>(std::max<uint64_t>((uint64_t)kH0GridHost * p.S * p.reg_cap,
-                                                (uint64_t)nbs * p.S * p.reg_cap_skew),
+                                                (uint64_t)kP0SkewBlocks * p.S * p.reg_cap_skew),
                              n + n / 4 + (uint64_t)4096 * p.S * kResShards);
   return p;
 }
@@ -631,7 +575,7 @@ P0Bufs p0_bufs(s3imph_ctx* c, uint64_t n, uint64_t n_geom, hipStream_t s, unsign
                bool want_x = false) {
   const uint64_t T = tiles_of(level_words(n_geom), tb, 0);
   uint64_t need = 0;
-  P0Bufs p = p0_geom(c, n, n_geom, tb, &need);
+  P0Bufs p = p0_geom(n, n_geom, tb, &need);
   // (a capacity is zeroed before its buffer is replaced and set only once the allocation
   // succeeded: a NOMEM leaves a null buffer that the next build reallocates, never one that a
   // smaller build would take as big enough)
@@ -686,62 +630,6 @@ bool p0_try_bufs(s3imph_ctx* c, uint64_t n, uint64_t n_geom, hipStream_t s, P0Bu
   }
 }
 
-// P0F (developer knob S3IMPH_P0F=1; off by default): level 1 of a P0 build fed by level 0's
-// tile kernel.  Bit-exact, but measured slower on C3 (level 1 -0.32 ms, the
-// count pass +0.15, the in-tile positions' partial-line writes +0.17, the fed tile +0.08)
-// The super-tile scatter overlapped on the level-0 hash (bit-exact, measured slower:
-// the hash loses more beside it than the scatter's time): S3IMPH_P0_OV=1 turns it on (developer
-// switch); S3IMPH_P0_DIRECT=1 runs the direct form alone after the hash (A/B knob)
-bool p0_ov_on() {
-  static const bool v = [] {
-    const char* e = dev_env("S3IMPH_P0_OV");
-    return e && std::atoi(e) != 0;
-  }();
-  return v;
-}
-bool p0_direct_on() {
-  static const bool v = [] {
-    const char* e = dev_env("S3IMPH_P0_DIRECT");
-    return e && std::atoi(e) != 0;
-  }();
-  return v;
-}
-
-// Overlap set-up, on s after the build's state init: every region fill open, no part done;
-// the overlapped scatter then starts on c->ov_stream (it spins on the fills the hash publishes)
-void p0_ov_launch(s3imph_ctx* c, const BinBuffers& b, P0Bufs& p, hipStream_t s) {
-  if (!c->ov_stream) {
-    HIPCHECK(hipStreamCreateWithFlags(&c->ov_stream, hipStreamNonBlocking));
-    for (auto& e : c->ov_ev) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  if (!c->p0_ov) dalloc(c->p0_ov, (uint64_t)kH0GridHost + 8ull * kP0OvChunks * kMaxRanks);
-  p.hxcc = c->p0_ov;
-  p.ov_done = c->p0_ov + kH0GridHost;
-  HIPCHECK(hipMemsetAsync(p.pcnt, 0xff, (uint64_t)kH0GridHost * p.S * sizeof(unsigned), s));
-  HIPCHECK(hipMemsetAsync(p.hxcc, 0xff, (uint64_t)kH0GridHost * sizeof(unsigned), s));
-  HIPCHECK(hipMemsetAsync(p.ov_done, 0, 8ull * kP0OvChunks * p.S * sizeof(unsigned), s));
-  HIPCHECK(hipEventRecord(c->ov_ev[0], s));
-  HIPCHECK(hipStreamWaitEvent(c->ov_stream, c->ov_ev[0], 0));
-  launch_p0_scatter_direct(b, p, true, c->ov_stream);
-  HIPCHECK(hipEventRecord(c->ov_ev[1], c->ov_stream));
-}
-
-bool p0f_on() {
-  static const bool v = [] {
-    const char* e = dev_env("S3IMPH_P0F");
-    return e && std::atoi(e) != 0;
-  }();
-  return v;
-}
-
-// P0F region capacity: level 0's tile kernel takes its tiles by ticket, so one block's share of
-// level 1's records follows its share of the tiles, not a Poisson fill: regions hold twice the
-// mean (a block would have to run twice its share of the tiles to overflow; then the build reruns)
-uint64_t p0f_region_cap(uint64_t n1, unsigned S) {
-  const double mean = (double)n1 / ((double)kP0FedGrid * S);
-  return (uint64_t)(2.0 * mean + 10.0 * std::sqrt(mean) + 256.0);
-}
-
 void enqueue_binned(s3imph_ctx* c, const uint8_t* blob, const uint64_t* offsets, const uint64_t* pos,
                     uint64_t n, uint64_t* fp_out, uint64_t* pos_out, hipStream_t s, bool conservative) {
   BinBuffers b = make_bufs(c, pos, fp_out, pos_out, s);
@@ -753,73 +641,17 @@ void enqueue_binned(s3imph_ctx* c, const uint8_t* blob, const uint64_t* offsets,
       T14 <= kP0MaxS * kP0MaxTps) {
     // level 0 in 2^14-position register tiles through super-tiles (s3imph_internal.h, P0); its
     // buffers (~1.2 n x 20 B) may not fit next to the workspace: then the split-kernel path.
-    // P0F: a level 1 past the reservation scatter's 4096 tiles (C3: 4.8k) is fed by level 0's
-    // tile kernel when its regions fit the super-tile buffer; level 0's scatter then also writes
-    // each slot's in-tile position for the count pass (k_p0_count).
-    const double n1m = (double)n * q;
-    const uint64_t ng1 = (uint64_t)(n1m * 1.02 + 6.0 * std::sqrt(n1m)) + 1024;  // level 1's size bound
-    const uint64_t T1 = tiles_of(level_words(ng1), kRegTileMaxBits, 0);
-    bool fed = p0f_on() && T1 > kScatterTiles && T1 <= kP0MaxS * kP0MaxTps;
     P0Bufs p;
-    if (p0_try_bufs(c, n, n, s, &p, kRegTileMaxBits, fed)) {
-      P0Bufs p1{};
-      if (fed) {  // level 1's super-tiles, its regions in c->p0_sup (free once level 0's scatter ran)
-        uint64_t need1 = 0;
-        p1 = p0_geom(c, ng1, ng1, kRegTileMaxBits, &need1);
-        p1.reg_cap = p0f_region_cap(ng1, p1.S);
-        fed = p1.S <= (unsigned)kMaxRanks && (uint64_t)kP0FedGrid * p1.S * p1.reg_cap <= c->p0_sup_cap &&
-              T1 <= c->p0_tiles && p0_fused(blob, p);
-        p1.sup = c->p0_sup;
-        p1.sup_cap = c->p0_sup_cap;
-        p1.nb = kP0FedGrid;
-        p1.pcnt = c->p0_pcnt;
-        p1.scnt = c->p0_scnt;
-        p1.bucket = p.bucket;  // (level 0's slots: read by its tile kernel before level 1's scatter)
-        p1.bucket_cap = p.bucket_cap;
-        p1.tcnt = p.tcnt;
-        p1.flags = p.flags;
-      }
-      if (!fed) p.x = nullptr;
+    if (p0_try_bufs(c, n, n, s, &p)) {
       const LevelGeom g0 = choose_geom(n, kTargetTiles0, chunks0(n), kRegTileMaxBits);
-      if (fed) {
-        const LevelsPlan P = plan_levels_from(c, b, 2, (uint64_t)(n1m * q), g0, false);
-        b.l20 = c->l20_mask = plan_l20(c, b, P, true, n);
-        launch_init_state(c->d_st, n, n, s, offsets);
-        ev_mark(c, s, "init");
-        launch_p0_hash(blob, offsets, n, b, g0, p, s);
-        ev_mark(c, s, "hash_part0");
-        launch_p0_scatter(b, p, true, s);
-        launch_p0_count(b, p, s);
-        ev_mark(c, s, "scatter0_p0");
-        const NextPart np{p1.sup, p1.reg_cap, p1.pcnt, p1.tps_sub(), p1.S, nullptr};
-        launch_p0_tile_fed(b, p, np, s);
-        ev_mark(c, s, "tile0_p0");
-        HIPCHECK(hipMemsetAsync(p1.tcnt, 0, c->p0_tiles * kResShards * sizeof(unsigned), s));
-        launch_p0_scatter(b, p1, true, s, 1);
-        launch_p0_tile_level(1, b, p1, s);
-        ev_mark(c, s, "level1_p0");
-        fault_dup_record(c, c->list[1], s, b.list20(2));
-        run_levels(c, b, P, 2, s);
-        return;
-      }
       // the list levels' plan first: level 0's tile kernel writes level 1's list as R20 or Rec
       const LevelsPlan P = plan_levels_from(c, b, 1, (uint64_t)((double)n * q), g0, false);
       b.l20 = c->l20_mask = plan_l20(c, b, P, true, n);
       launch_init_state(c->d_st, n, n, s, offsets);
       ev_mark(c, s, "init");
-      // the super-tile scatter overlapped on the hash (fused regions of a device-resident set)
-      const bool ov = p0_ov_on() && p0_fused(blob, p) && !b.feed && p.tps <= 1024;
-      if (ov) p0_ov_launch(c, b, p, s);
       launch_p0_hash(blob, offsets, n, b, g0, p, s);
       ev_mark(c, s, "hash_part0");
-      if (ov) {
-        HIPCHECK(hipStreamWaitEvent(s, c->ov_ev[1], 0));
-        launch_p0_scatter_direct(b, p, false, s);
-      } else if (p0_direct_on() && p0_fused(blob, p) && p.tps <= 1024) {
-        launch_p0_scatter_direct(b, p, false, s);
-      } else {
-        launch_p0_scatter(b, p, p0_fused(blob, p), s);
-      }
+      launch_p0_scatter(b, p, p0_fused(blob, p), s);
       ev_mark(c, s, "scatter0_p0");
       launch_p0_tile(b, p, s);
       ev_mark(c, s, "tile0_p0");
@@ -2192,7 +2024,7 @@ int dist_attempt_bitmap(s3imph_ctx* c, const uint8_t* blob, const uint64_t* offs
       if (Td1 > bm_target_tiles() && Td1 <= kBmMaxTiles) {
         const uint64_t np1 = (uint64_t)(npred * q * 1.1) + 4096;
         uint64_t need1 = 0;
-        const P0Bufs g1 = p0_geom(c, np1, ng1, tbd, &need1);
+        const P0Bufs g1 = p0_geom(np1, ng1, tbd, &need1);
         nb1 = bm_settle_grid(tiles, bm_settle_threads(tb, P, true));
         rc1 = p0_region_cap(np1, g1.S, nb1);
         if (g1.S <= (unsigned)kMaxRanks && c->p0_sup && c->p0_pcnt &&
@@ -3059,15 +2891,13 @@ int s3imph_ctx_create(int device, s3imph_ctx** out, char* err, size_t errlen) {
     if (const char* m = dev_env("S3IMPH_RES_MAX")) c->res_max_keys = std::strtoull(m, nullptr, 10);
     if (const char* m = dev_env("S3IMPH_RES_FILL")) c->res_fill = std::strtoull(m, nullptr, 10);
     if (const char* m = dev_env("S3IMPH_RES0")) c->res0 = std::atoi(m);
-    c->loose_geom = dev_env("S3IMPH_LOOSE_GEOM") != nullptr;
-    c->route_self = dev_env("S3IMPH_DIST_ROUTE_SELF") != nullptr;  // A/B knob: list-level geometry from 1.1x bounds
+    c->route_self = dev_env("S3IMPH_DIST_ROUTE_SELF") != nullptr;
     c->debug = std::getenv("S3IMPH_DEBUG") != nullptr;
     c->fault_dup = dev_env("S3IMPH_FAULT_DUP_REC") != nullptr;
     if (const char* m = dev_env("S3IMPH_P0")) c->p0 = std::atoi(m);
     if (const char* m = dev_env("S3IMPH_L20")) c->l20 = std::atoi(m) != 0;
     if (const char* m = dev_env("S3IMPH_BM_LANES")) c->bm_counts = std::strcmp(m, "counts") == 0;
     if (const char* m = dev_env("S3IMPH_SCAT_CFG")) c->scat_cfg = std::atoi(m);
-    if (const char* m = dev_env("S3IMPH_SKEW_CFG")) c->skew_cfg = std::atoi(m);
     if (const char* m = dev_env("S3IMPH_DIST_SWITCH")) c->dist_switch = std::strtoull(m, nullptr, 10);
     if (const char* m = std::getenv("S3IMPH_DIST_MODE")) c->d.mode = std::strcmp(m, "bitmap") == 0 ? kDistBitmap : kDistRoute;
     // A blocking stream: implicitly ordered with the legacy NULL stream, so work a
@@ -3115,9 +2945,6 @@ int s3imph_ctx_destroy(s3imph_ctx* c) {
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   for (hipEvent_t e : c->copy_evs)
-    if (e) (void)hipEventDestroy(e);
-  if (c->ov_stream) (void)hipStreamDestroy(c->ov_stream);
-  for (hipEvent_t e : c->ov_ev)
     if (e) (void)hipEventDestroy(e);
   delete c;
   return S3IMPH_OK;

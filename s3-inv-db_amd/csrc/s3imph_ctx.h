@@ -242,8 +242,7 @@ struct s3imph_ctx {
   s3imph::FinScratch* fin = nullptr;  // finalize-pass scratch (s3imph_finalize.hip), lazily made
   s3imph::AggScratch* agg = nullptr;  // aggregation scratch and the last plan (s3imph_aggregate.hip), lazily made
   s3imph::SortScratch* srt = nullptr;  // listing sort / gather scratch (s3imph_sort.hip), lazily made
-  uint32_t* mid = nullptr;            // k_mid_levels scratch (kMidScratchU32, or the 256-workgroup form's), lazily made
-  uint64_t mid_cap = 0;               // ... its u32 words
+  uint32_t* mid = nullptr;            // k_mid_levels scratch (kMidScratchU32), lazily made
   Rec* split = nullptr;               // k_tile_split scratch, made for sets big enough for 2^15+ tiles
   hipStream_t own_stream = nullptr;
   std::mutex mu;
@@ -272,9 +271,7 @@ struct s3imph_ctx {
   // res0 = 0 puts level 0 on the counted path, 2 on the reservation path whatever its fill
   int res0 = 1;  // level 0 through the reservation scatter when its tiles are large
   bool route_self = false;  // S3IMPH_DIST_ROUTE_SELF: a one-rank sharded build routes like P > 1 (tests)
-  int scat_cfg = 2;         // S3IMPH_SCAT_CFG: reservation-scatter forms (launch_binned_scatter_res)
-  int skew_cfg = 2;         // S3IMPH_SKEW_CFG: skewed-length hash block / group shape (launch_hash_skew)
-  bool loose_geom = false;  // S3IMPH_LOOSE_GEOM: list levels sized from 1.1x (not 1.02x + 6 sigma) bounds
+  int scat_cfg = 2;         // S3IMPH_SCAT_CFG=0: the 4096-counter reservation scatter on small sets (test hook)
   // P0 level 0 (s3imph_internal.h): tile slot fills / look-back words for up to p0_tiles
   // 2^14-position tiles, super-tile slot fills; made on first use.  S3IMPH_P0=0 keeps such
   // sets on the split kernel (A/B knob).
@@ -288,12 +285,6 @@ struct s3imph_ctx {
   uint64_t p0_sup_cap = 0;
   uint16_t* p0_x = nullptr;       // bitmap decomposition: in-tile position of each level-0 R20 slot
   uint64_t p0_x_cap = 0;
-  // level 0's super-tile scatter overlapped on the hash: its stream, the events that order it
-  // (after the build's state init / before the follow-up scatter), and the hash blocks' XCDs +
-  // the finished parts (kH0GridHost + 8 kP0OvChunks kMaxRanks u32)
-  hipStream_t ov_stream = nullptr;
-  hipEvent_t ov_ev[2] = {};
-  unsigned* p0_ov = nullptr;
   // R20 list levels (BinBuffers::l20): on unless S3IMPH_L20=0 (A/B knob); l20_mask is the
   // last build's mask (classify_stop reads its stop level's list in that format)
   bool l20 = true;

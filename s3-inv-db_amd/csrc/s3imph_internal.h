@@ -55,12 +55,6 @@ struct LevelState {
   unsigned long long dS[kMaxLevels + 2];       // words per rank range (owner = word / dS)
   unsigned long long dmagic[kMaxLevels + 2];   // Barrett reciprocal of dS
   unsigned long long gn[kMaxLevels + 2];       // global key count of level L
-  // P0F (single GPU): level 0's settled keys, counted before its tile kernel (k_p0_count)
-  unsigned long long settled0;
-  // P0 overlap (single GPU): level-0 hash blocks done, the overlapped scatter's per-XCD tickets
-  unsigned int h0_done;
-  unsigned int mid_bar2;  // k_mid_levels<kMidGBig>'s grid-barrier counter (zeroed by k_init_state)
-  unsigned long long ov_ticket[8];
 };
 
 #if defined(__HIPCC__)
@@ -182,18 +176,11 @@ constexpr uint64_t kMidTot = kMidXc + (uint64_t)kMidG * kMidG;  // even: u64-ali
 constexpr uint64_t kMidXb = kMidTot + 2 * kMidG + 16;          // 16-byte aligned
 constexpr uint64_t kMidScratchU32 = kMidXb + (uint64_t)kMidG * kMidG * kMidSeg * 6;
 constexpr double kMidMargin = 1.15;  // a level predicted above kMidMaxKeys / kMidMargin stays binned
-// The same kernel over every CU (k_mid_levels<kMidGBig>) for the levels above kMidMaxKeys up to
-// kMidMaxKeysBig (owners again average <= 6.9k of 8k slots; a level's size is predicted within
-// 2 % + 6 sigma, the bound the binned geometry uses): per-(owner, sender) segments of kMidSegBig
-// records (a sender's <= 8192 records over 256 owners: 32 on average), its own barrier counter.
-constexpr int kMidGBig = 256;
-constexpr unsigned kMidSegBig = 128;
-constexpr unsigned long long kMidMaxKeysBig = 1750ull << 10;
-constexpr uint64_t kMidBigMinKeys = 1ull << 20;  // sets this big get the 256-workgroup scratch
+// k_mid_levels<G>'s scratch layout
 template <int G>
 struct MidCfg {
-  static constexpr unsigned kSeg = G == kMidG ? kMidSeg : kMidSegBig;
-  static constexpr unsigned long long kMax = G == kMidG ? kMidMaxKeys : kMidMaxKeysBig;
+  static constexpr unsigned kSeg = kMidSeg;
+  static constexpr unsigned long long kMax = kMidMaxKeys;
   static constexpr uint64_t kW32 = 2 * ((2 * kMax + 63) / 64);  // u32 words of the largest level
   // scratch (u32 units): 64 unused, segment counts [G][G], per-owner totals [G] u64, exchange [G][G][kSeg] Rec
   static constexpr uint64_t kXc = 64;
@@ -202,7 +189,6 @@ struct MidCfg {
   static constexpr uint64_t kScratchU32 = kXb + (uint64_t)G * G * kSeg * 6;
 };
 static_assert(MidCfg<kMidG>::kXb == kMidXb && MidCfg<kMidG>::kScratchU32 == kMidScratchU32, "mid scratch layout");
-static_assert(MidCfg<kMidGBig>::kTot % 2 == 0 && MidCfg<kMidGBig>::kXb % 4 == 0, "mid scratch alignment");
 constexpr int kTailThreads = 1024;
 constexpr int kTailLdsWords32 = 2 * 2 * ((kGammaNum * kTailKeys + 63) / 64);  // A and C, u32 words
 
@@ -262,7 +248,6 @@ struct BinBuffers {
   Rec* split;                           // k_tile_split scratch (split_scratch_records()), or null
   int scat_cfg = 2;                     // k_scatter_res forms (launch_binned_scatter_res)
   bool pipe_tiles = false;              // 2^14 reservation tiles on k_tile_p0 (else k_tile_reg)
-  int skew_cfg = 2;                     // k_hash_skew block / group shape (launch_hash_skew)
   // bit L (L >= 1): level L's input list holds R20 records (k, f, key index; identity
   // positions) instead of Rec: its producer (k_tile_p0 / k_tile_split of level L - 1) writes
   // them, its reservation scatter reads them and keeps them R20 in the slots, and its tile
@@ -289,12 +274,11 @@ constexpr uint64_t kP0TargetTps = 512;
 // 64 x 8 in two same-box sweeps, `gpurun_out` r4_sweep / r4_sweep2)
 constexpr unsigned kP0ScatterBlocks = 768;
 // at most 64 super-tiles (C3: 64).  k_scatter_p0 gives each one max(256 / S, 8) blocks of 1024
-// threads, a multiple of 8 (past 32 super-tiles: 512 blocks in two waves over the CUs; with
-// S3IMPH_P0_BIG=0, 8 blocks of 512 threads, two per CU), so the records of a tile arrive through
-// all kResShards XCD shards (4 blocks per super-tile filled only 4 of a tile's 8 shard slots:
-// twice their capacity on average, C3 overflowed into the rerun).  S3IMPH_P0_MAXS lowers the cap.
+// threads, a multiple of 8 (past 32 super-tiles: 512 blocks in two waves over the CUs), so the
+// records of a tile arrive through all kResShards XCD shards (4 blocks per super-tile filled only
+// 4 of a tile's 8 shard slots: twice their capacity on average, C3 overflowed into the rerun).
+// S3IMPH_P0_MAXS lowers the cap.
 constexpr uint64_t kP0MaxS = 64;
-constexpr unsigned kP0OneBlockS = 32;  // the most super-tiles the 256 blocks of one wave cover
 constexpr uint64_t kP0MaxKeys = 1ull << 31;  // bucket slot indices stay below 2^32
 // A level-0 record with an identity position: k (2 dwords), f (2), key index i (p = pos_base + i).
 struct R20 {
@@ -306,7 +290,7 @@ struct P0Bufs {
                                // (fused hash), or S x kResShards slots of sup_cap / (S kResShards) (pass)
   uint64_t sup_cap = 0;        // R20 records in sup
   uint64_t reg_cap = 0;
-  uint64_t reg_cap_skew = 0;   // the same for k_hash_skew's p0_skew_blocks blocks (a skewed set)
+  uint64_t reg_cap_skew = 0;   // the same for k_hash_skew's kP0SkewBlocks blocks (a skewed set)
   unsigned* pcnt = nullptr;    // region fills (kH0Grid x S), written by the hash
   unsigned* scnt = nullptr;    // super-tile slot fills (S x kResShards), zeroed before the build
   R20* bucket = nullptr;       // tile slots (T x kResShards)
@@ -319,11 +303,6 @@ struct P0Bufs {
   uint16_t* x = nullptr;       // bitmap decomposition: each slot's position in its tile (the mark's input)
   unsigned nb = 0;             // the regions' producer blocks (0: the level-0 hash's grid; a bitmap
                                // list level fed by the previous settle: its grid, NextPart)
-  // level 0 with the super-tile scatter overlapped on the hash (single GPU, fused regions):
-  // each hash block's XCD (kH0GridHost) and the parts the overlapped launch finished
-  // (8 kP0OvChunks x S); null otherwise
-  unsigned* hxcc = nullptr;
-  unsigned* ov_done = nullptr;
   // super-tiles in 2^14-position units (tps tiles of 2^tb): the partition passes cut
   // (position >> 14) by this, so they need not know tb
   unsigned tps_sub() const { return tps << (tb - kRegTileMaxBits); }
@@ -337,22 +316,9 @@ void launch_p0_scatter(const BinBuffers& b, const P0Bufs& p, bool fused, hipStre
 void launch_p0_partition_list(int level, const BinBuffers& b, const P0Bufs& p, hipStream_t s);
 bool p0_fused(const uint8_t* blob, const P0Bufs& p);  // the hash partitions (aligned blob, S <= kMaxRanks)
 uint64_t p0_region_cap(uint64_t n, unsigned S, unsigned blocks);  // records per (hash block, super-tile) region
-unsigned p0_skew_blocks(int skew_cfg);               // k_hash_skew's grid (its fused partition's blocks)
+constexpr unsigned kP0SkewBlocks = 256;              // k_hash_skew's grid (its fused partition's blocks)
 constexpr int kH0GridHost = 4096;                    // = k_hash0_pair's grid (kH0Grid)
-constexpr int kP0FedGrid = 256;                      // P0F: level 0's tile kernel blocks (level 1's region producers)
 void launch_p0_tile(const BinBuffers& b, const P0Bufs& p, hipStream_t s);
-// level 0's super-tile scatter in its direct form: ov, the persistent launch beside the hash;
-// otherwise the follow-up over the parts it left (or all of them)
-constexpr unsigned kP0OvChunks = 8;  // hash-block chunks per XCD (kH0GridHost / 64 blocks each)
-void launch_p0_scatter_direct(const BinBuffers& b, const P0Bufs& p, bool ov, hipStream_t s);
-// P0F: level 1 fed by level 0's tile kernel (s3imph_binned.hip).  launch_p0_count: level 0's
-// settled keys from the slots' in-tile positions (p.x), then level 1 sized on the device;
-// launch_p0_tile_fed: level 0's tiles with the collided records into level 1's super-tile
-// regions (np); launch_p0_tile_level: a list level's 2^14 tiles from the super-tile slots
-void launch_p0_count(const BinBuffers& b, const P0Bufs& p, hipStream_t s);
-struct NextPart;
-void launch_p0_tile_fed(const BinBuffers& b, const P0Bufs& p, const NextPart& np, hipStream_t s);
-void launch_p0_tile_level(int level, const BinBuffers& b, const P0Bufs& p, hipStream_t s);
 void binned_set_lds_limits();
 void launch_binned_count(int level, const uint8_t* blob, const uint64_t* offsets, uint64_t n, const BinBuffers& b,
                          LevelGeom g, int grid_chunks, hipStream_t s, bool histogram = true);
@@ -364,9 +330,8 @@ void launch_binned_tile(int level, const BinBuffers& b, LevelGeom g, int grid_ti
 void launch_binned_scatter_res(int level, const BinBuffers& b, LevelGeom g, int grid, hipStream_t s,
                                uint64_t i_lo = 0, uint64_t i_hi = 0, uint64_t tmax = 0);
 void launch_binned_tail(int first_level, int big_launched, const BinBuffers& b, hipStream_t s);
-// levels L0..L1 (each predicted above the tail and at most kMidMaxKeys keys; big: at most
-// kMidMaxKeysBig, over kMidGBig workgroups) in one launch
-void launch_binned_mid(int L0, int L1, const BinBuffers& b, hipStream_t s, bool big = false);
+// levels L0..L1 (each predicted above the tail and at most kMidMaxKeys keys) in one launch
+void launch_binned_mid(int L0, int L1, const BinBuffers& b, hipStream_t s);
 
 // ---- multi-GPU launchers (s3imph_dist.hip) ------------------------------------------
 constexpr int kMaxRanks = 64;

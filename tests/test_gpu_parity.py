@@ -460,38 +460,18 @@ def test_small_level_paths_bit_exact(s3, oracle_lib, res_max, monkeypatch):
         c.close()
 
 
-@pytest.mark.parametrize("cfg", ["0", "1"])
+@pytest.mark.parametrize("cfg", ["0"])
 def test_scatter_forms_bit_exact(s3, oracle_lib, cfg, monkeypatch):
-    """The reservation scatter's other LDS forms (S3IMPH_SCAT_CFG 0: 4096 tile counters and
-    4096-record rounds for every level; 1: counters sized to the level's tiles, 4096-record
-    rounds) on a set whose levels take 1221 / 481 / 189 tiles: bit-exact with the oracle,
-    like the default form (5120-record rounds) in test_c2_10m_bit_exact."""
+    """The reservation scatter's 4096-counter form (S3IMPH_SCAT_CFG=0: 4096 tile counters and
+    4096-record rounds for every level, which by default only levels of more than 2048 tiles
+    take) on a set whose levels take 1221 / 481 / 189 tiles: bit-exact with the oracle, like
+    the default form (counters sized to the level's tiles, 5120-record rounds) in
+    test_c2_10m_bit_exact."""
     monkeypatch.setenv("S3IMPH_SCAT_CFG", cfg)
     c = s3.DeviceBuilder(0)
     try:
         n = 10_000_000
         blob, offs = s3.gen_keys(0, 42, 32, 0, n)
-        st, fp, po, mph = oracle_lib.build(blob[: offs[-1]], offs)
-        assert st == 0
-        gfp, gpo, gmph, info = _device_build(s3, c, blob, offs)
-        assert gmph == mph
-        assert np.array_equal(gfp, fp)
-        assert np.array_equal(gpo, po)
-    finally:
-        c.close()
-
-
-@pytest.mark.parametrize("cfg", ["0", "1"])
-def test_skew_shapes_bit_exact(s3, oracle_lib, cfg, monkeypatch):
-    """The skewed-length hash's other block / group shapes (S3IMPH_SKEW_CFG 0: two 512-thread
-    blocks per CU with 2048-key groups; 1: 1024 threads with 4096-key groups) on a C5-style
-    log-uniform 1-1024 B set: bit-exact with the oracle, like the default 768 / 5120 shape
-    in test_c5_one_gpu_share_bit_exact."""
-    monkeypatch.setenv("S3IMPH_SKEW_CFG", cfg)
-    c = s3.DeviceBuilder(0)
-    try:
-        n = 3_000_000
-        blob, offs = s3.gen_keys(1, 23, 0, 0, n)
         st, fp, po, mph = oracle_lib.build(blob[: offs[-1]], offs)
         assert st == 0
         gfp, gpo, gmph, info = _device_build(s3, c, blob, offs)
@@ -767,39 +747,12 @@ def _parity_device_subprocess(env: dict, cases, builds: int = 2) -> None:
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
 
 
-def test_p0_scatter_overlapped_on_hash_bit_exact(s3, oracle_lib):
-    """Level 0's super-tile scatter overlapped on the hash (S3IMPH_P0_OV=1): the
-    direct-form scatter runs beside k_hash0_pair on a second stream, taking each XCD's parts as
-    their hash blocks publish them, the follow-up launch the rest; then the direct form alone
-    (S3IMPH_P0_DIRECT=1).  Uniform sets at 509 / 191 / 1024-tile super-tiles (C3 100M and
-    smaller) and a skewed set (the follow-up takes every part): bit-exact, two builds each."""
-    cases = [(100_000_000, 0, 64), (30_000_000, 0, 16), (40_000_000, 1, 0)]
-    _parity_device_subprocess({"S3IMPH_DEV": "1", "S3IMPH_P0_OV": "1"}, cases)
-    _parity_device_subprocess({"S3IMPH_DEV": "1", "S3IMPH_P0_OV": "1", "S3IMPH_P0_TPS": "191"}, cases[:1], builds=1)
-    _parity_device_subprocess({"S3IMPH_DEV": "1", "S3IMPH_P0_OV": "1", "S3IMPH_P0_MAXS": "4"}, cases[1:2], builds=1)
-    _parity_device_subprocess({"S3IMPH_DEV": "1", "S3IMPH_P0_DIRECT": "1"}, cases[:2], builds=1)
-
-
-def test_mid_levels_over_every_cu_bit_exact(s3, oracle_lib):
-    """The mid-size levels on 256 workgroups (S3IMPH_MID_BIG=1: the levels of 440k-1.75M keys;
-    =2: every level down to the tail; off by default): C2's 10M keys and a skewed
-    4M set, bit-exact, two builds each (the second reuses the 256-workgroup scratch)."""
-    _parity_device_subprocess({"S3IMPH_DEV": "1", "S3IMPH_MID_BIG": "1"}, [(10_000_000, 0, 32), (4_000_000, 1, 0)])
-    _parity_device_subprocess({"S3IMPH_DEV": "1", "S3IMPH_MID_BIG": "2"}, [(10_000_000, 0, 32)], builds=1)
-
-
 def test_p0_many_super_tiles_bit_exact(s3, oracle_lib):
-    """More than 32 super-tiles on the two-block-per-CU super-tile scatter (S3IMPH_P0_BIG=0,
-    S3IMPH_P0_TPS=48: 45 / 51 super-tiles on 17.5M uniform / 20M skewed keys, 8 blocks of 512
-    threads each), reading the fused hash's regions and k_hash_skew's; bit-exact."""
-    _parity_subprocess({"S3IMPH_P0_TPS": "48", "S3IMPH_P0_BIG": "0"}, [(17_500_000, 0, 20), (20_000_000, 1, 0)])
-
-
-def test_skew_partition_two_blocks_bit_exact(s3, oracle_lib):
-    """k_hash_skew's partition form without result arrays, two 512-thread blocks per CU
-    (S3IMPH_SKEW_CFG=3; off by default, profiles/r6_skew/): a 20M-key skewed set through
-    P0's 512 region sets, bit-exact."""
-    _parity_subprocess({"S3IMPH_SKEW_CFG": "3"}, [(20_000_000, 1, 0)])
+    """More than 32 super-tiles on the super-tile scatter (S3IMPH_P0_MIN_TILES=16,
+    S3IMPH_P0_TPS=16: 5M keys are 611 2^14-position tiles in 39 super-tiles of 16, 16 blocks of
+    1024 threads each on the 256-counter form), reading the fused hash's regions (uniform keys)
+    and k_hash_skew's (skewed keys); bit-exact."""
+    _parity_subprocess({"S3IMPH_P0_MIN_TILES": "16", "S3IMPH_P0_TPS": "16"}, [(5_000_000, 0, 20), (5_000_000, 1, 0)])
 
 
 def test_p0_super_tile_cap_bit_exact(s3, oracle_lib):
@@ -831,12 +784,3 @@ def test_piecewise_hash_every_level0_path(s3, oracle_lib):
     Bit-exact vs the oracle."""
     _parity_subprocess({"S3IMPH_PIECE_BITS": "20"},
                        [(3_000_000, 0, 24, True), (2_000_000, 0, 32), (1_500_000, 1, 0), (18_000_000, 0, 20)])
-
-
-def test_p0f_fed_level1_bit_exact(s3, oracle_lib):
-    """P0F (developer knob S3IMPH_P0F=1): level 1 of a 90M-key P0 build (4.4k 2^14
-    tiles, past the reservation scatter's 4096) fed by level 0's tile kernel — a count pass
-    over the slots' in-tile positions sizes level 1 first, level 0's tiles write level 1's
-    records straight into its super-tile regions, level 1 runs the super-tile scatter and the
-    register tiles; a skewed 90M set the same way: bit-exact vs the oracle."""
-    _parity_subprocess({"S3IMPH_P0F": "1"}, [(90_000_000, 0, 24), (90_000_000, 1, 0)])
