@@ -547,7 +547,10 @@ int s3imph_index_from_objects_host(int device, const uint8_t *keys, const uint64
 
 /* Mapping.FromS3 (tiers.go:85-115): both arguments trimmed of white space and upper-cased
  * (NULL = ""); INTELLIGENT_TIERING takes its tier from access_tier (FREQUENT when that is
- * missing or unknown); an unknown storage class is STANDARD.  Host-only, no device call. */
+ * missing or unknown); an unknown storage class is STANDARD.  White space is the ASCII set
+ * (\t \n \v \f \r and space), the library's one trim rule; the reference's strings.TrimSpace
+ * also trims Unicode white space, which S3 does not write.  The CSV parse of section 5g applies
+ * the same function on the device, per record. */
 int s3imph_tier_from_s3(const char *storage_class, const char *access_tier);
 /* Info.Name ("STANDARD", "GLACIER", ...) and Info.FilePrefix ("standard", "glacier_fr", ...) of
  * tiers.go:39-53; NULL for id >= S3IMPH_NUM_TIERS. */
@@ -694,6 +697,118 @@ int s3imph_sort_objects_host(int device, const uint8_t *keys, const uint64_t *ke
 int s3imph_index_from_unsorted_objects_host(int device, const uint8_t *keys, const uint64_t *key_offsets,
                                             const uint64_t *sizes, const uint8_t *tiers, uint64_t m,
                                             uint32_t max_depth, const char *out_dir, char *err, size_t errlen);
+
+/* ------------------------------------------------------------------------
+ * 5g. S3 inventory CSV text -> the object listing of sections 5d / 5f, on the GPU: what
+ *     pkg/inventory's CSVReader.Read (reader.go:250-297) and csvInventoryReader.Next
+ *     (unified.go:121-161) return, record for record and in file order — the key blob, m + 1
+ *     offsets, the sizes and the tier ids, ready for s3imph_sort_objects_device and
+ *     s3imph_aggregate_plan[_tiers]_device.  The input is decompressed CSV bytes, usually
+ *     without a header row (an S3 inventory has none; its manifest's fileSchema names the columns).
+ *
+ *     Parity is "vs restated spec", as for mph.bin (DESIGN.md sections 2 and 4.5d): Go's
+ *     encoding/csv is restated, not linked.  The restatement is csv.Reader.readRecord with
+ *     Comma = ',', no comment character, LazyQuotes = true, TrimLeadingSpace = false and
+ *     FieldsPerRecord = -1:
+ *       1. A '\r' is deleted when the next byte is '\n' or when it is the buffer's last byte
+ *          (readLine's CRLF rule), inside quoted fields too; any other '\r' is data.
+ *       2. Five states over the bytes left — R record start, F field start after a comma, U in
+ *          an unquoted field, Q in a quoted field, E in a quoted field just after a '"':
+ *            state  '"'            ','             '\n'                      other byte c
+ *            R      -> Q           end field -> F  -> R (empty line)         emit c -> U
+ *            F      -> Q           end field -> F  end field + record -> R   emit c -> U
+ *            U      emit '"' -> U  end field -> F  end field + record -> R   emit c -> U
+ *            Q      -> E           emit -> Q       emit -> Q                 emit c -> Q
+ *            E      emit '"' -> Q  end field -> F  end field + record -> R   emit '"', c -> Q
+ *          The end of the buffer in any state but R ends the field and the record.  Every byte
+ *          string parses; there is no error.
+ *       3. Per record: dropped when it has <= key_col or <= size_col fields (n_short), or an
+ *          empty key field (n_empty_key).  The key is the field's emitted bytes, unchanged: no
+ *          URL decoding, no UTF-8 validation, 0x00 and bytes >= 0x80 are ordinary.  The size is
+ *          the field trimmed of white space at both ends, which must then be one or more ASCII
+ *          digits of value <= 2^64 - 1 (strconv.ParseUint base 10: no sign, no '_', not empty,
+ *          leading zeros allowed); anything else is size 0 (n_bad_size counts the kept records
+ *          where that happened).  The tier is s3imph_tier_from_s3(storage, access_tier) on the
+ *          two fields; a column that is -1 or beyond the record's fields gives "".
+ *     White space is the ASCII set of s3imph_tier_from_s3 — one rule for tier names, header
+ *     names and sizes; the reference trims Unicode white space as well.
+ *
+ *     Out of scope: gzip (the caller inflates), Parquet, a listing larger than one GPU's memory,
+ *     the multi-GPU builds.
+ *
+ *     Memory: the scratch lives in ctx, grows on demand and is released by
+ *     s3imph_release_workspaces: 1/16 byte per input byte (a 2-byte state map per 32-byte run; 11
+ *     bytes per 8 KiB tile besides), 41 bytes per record (its end, two scans, the key's source,
+ *     the size: 5 x 8; the tier: 1) and 8 bytes per object during the fill, plus the scans'
+ *     temporary.  A record far longer than a tile — only an unbalanced quote makes one — is walked
+ *     by one lane: correct, and slow.
+ * ------------------------------------------------------------------------ */
+typedef struct s3imph_csv_schema {
+    int32_t key_col, size_col, storage_col, access_tier_col;  /* the last two may be -1 */
+} s3imph_csv_schema;
+
+typedef struct s3imph_csv_info {
+    uint64_t n_records;    /* records read (csv.Reader.Read calls that returned one) */
+    uint64_t n_objects;    /* records kept: the listing's m */
+    uint64_t key_bytes;    /* bytes of their keys */
+    uint64_t n_short;      /* dropped: too few fields (reader.go:261) */
+    uint64_t n_empty_key;  /* dropped: empty key (reader.go:267) */
+    uint64_t n_bad_size;   /* kept with size 0 because the size did not parse (reader.go:273-276) */
+} s3imph_csv_info;         /* 48 bytes */
+
+/* The header row (OpenFileWithOptions, reader.go:96-135), host only: parses the first record by
+ * the rules above and matches "key", "size", "storageclass", "intelligenttieringaccesstier"
+ * against each field trimmed and ASCII-lower-cased; the last match wins; columns not found are
+ * -1.  *data_start = the byte offset where the data rows begin (pass csv + *data_start on).
+ * S3IMPH_ERR_FORMAT with "CSV header missing 'Key' column" / "CSV header missing 'Size' column"
+ * (ErrNoKeyColumn / ErrNoSizeColumn) or, for a buffer without a record, "read CSV header: EOF". */
+int s3imph_csv_header_schema(const uint8_t *csv, uint64_t len, s3imph_csv_schema *schema,
+                             uint64_t *data_start, char *err, size_t errlen);
+
+/* Every pass needed to know n_objects and key_bytes of one CSV buffer in HBM; fills *info and
+ * keeps the plan in ctx (a later plan replaces it), as the aggregate plan is kept.  d_csv may
+ * have any byte alignment and is readable up to round_up(len, 8) from its start; it must stay
+ * valid and unchanged until the fill.  len == 0 is OK with zeros in *info.  Null arguments,
+ * key_col < 0 or size_col < 0 are S3IMPH_ERR_INVALID before any device work; n_objects >= 2^32
+ * is S3IMPH_ERR_INVALID (the listing sort's limit; message: s3imph_ctx_last_error, "csv: ...")
+ * and leaves no plan.  Synchronous on `stream`. */
+int s3imph_csv_plan_device(s3imph_ctx *ctx, const uint8_t *d_csv, uint64_t len,
+                           const s3imph_csv_schema *schema, s3imph_csv_info *info, void *stream);
+
+/* The plan's objects: the key bytes at d_keys + key_base, n_objects + 1 offsets in
+ * d_key_offsets starting at key_base, n_objects entries of d_sizes and d_tiers (d_tiers NULL:
+ * no tiers).  key_base != 0 appends file after file into one listing: the next file's offsets
+ * pointer is d_key_offsets + n_objects and its key_base the last offset written.  The bytes from
+ * key_base + key_bytes up to round_up(key_base + key_bytes, 8) are written as zeros, bytes below
+ * key_base are left alone; keys_cap (bytes of d_keys from its start) below that rounded end is
+ * S3IMPH_ERR_INVALID.  S3IMPH_ERR_STATE without a plan.  The plan stays: a fill may be repeated.
+ * Synchronous on `stream`. */
+int s3imph_csv_fill_device(s3imph_ctx *ctx, uint8_t *d_keys, uint64_t keys_cap, uint64_t key_base,
+                           uint64_t *d_key_offsets, uint64_t *d_sizes, uint8_t *d_tiers, void *stream);
+
+/* The same from host memory (H2D, plan, fill, D2H): replaces the CSVReader.Read loop.  The four
+ * arrays are allocated by the library (release each with s3imph_free); the offsets start at 0.
+ * No object: *key_offsets = [0] and the others NULL or empty; len == 0 touches no device. */
+int s3imph_csv_parse_host(int device, const uint8_t *csv, uint64_t len, const s3imph_csv_schema *schema,
+                          uint8_t **keys, uint64_t **key_offsets, uint64_t **sizes, uint8_t **tiers,
+                          s3imph_csv_info *info, char *err, size_t errlen);
+
+/* CSV buffers in, index directory out.  Each buffer is parsed on its own — state R at its start,
+ * the end of the buffer at its end, so a lone quote in one file never swallows the next — and the
+ * buffers' objects are appended in order into one listing on the device (each buffer's device
+ * copy is freed after its fill).  From there exactly the path of
+ * s3imph_index_from_unsorted_objects_host, in the same device residency; with_tiers != 0 writes
+ * the tier files of section 5e.  *info_total (nullable) sums the buffers' infos.  A missing
+ * out_dir is S3IMPH_ERR_IO before the device is selected; the out-of-memory retry of the host
+ * builds applies; failures of the parse are worded "csv: ...". */
+int s3imph_index_from_csv_host(int device, const uint8_t *const *csv, const uint64_t *csv_len,
+                               uint64_t n_files, const s3imph_csv_schema *schema, int with_tiers,
+                               uint32_t max_depth, const char *out_dir, s3imph_csv_info *info_total,
+                               char *err, size_t errlen);
+
+/* The automaton passes' geometry, for tests that place events on the edges: a lane walks a run of
+ * *run_bytes, a workgroup a tile of *tile_bytes. */
+void s3imph_csv_geometry(uint32_t *run_bytes, uint32_t *tile_bytes);
 
 /* ------------------------------------------------------------------------
  * 6. Deterministic synthetic prefix sets (bench/test support, not on the path).

@@ -689,6 +689,7 @@ struct DevRows {
   // with tiers: kNT columns of n entries each, the present tiers
   uint64_t *tier_count = nullptr, *tier_bytes = nullptr;
   uint64_t present_mask = 0;
+  uint64_t m = 0;  // objects of the listing the rows were made from
 };
 
 // The listing's device copy put into byte order (s3imph_sort.hip): sort, gather out of place,
@@ -727,13 +728,28 @@ int sort_listing(s3imph_ctx* c, DevGuard& g, uint8_t*& d_keys, uint64_t*& d_koff
 
 // H2D of the listing, plan, fill (with `tiers`: the tier forms and the tier columns too; with
 // `unsorted`: the sort and the gather first); the listing's device copy is freed before returning.
+// With `csv` the listing comes from CSV buffers parsed on the device (s3imph_csv.hip), always in
+// file order, so sorted here; `tiers` then only says whether tiers are wanted.  No object at all:
+// out->m == 0 and no rows.
 int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes,
                    uint64_t m, uint32_t max_depth, DevRows* out, std::string* msg, const uint8_t* tiers = nullptr,
-                   bool unsorted = false) {
+                   bool unsorted = false, const CsvFiles* csv = nullptr) {
   hipStream_t s = c->own_stream;
   uint8_t *d_keys = nullptr, *d_tiers = nullptr;
   uint64_t *d_koff = nullptr, *d_sizes = nullptr;
-  if (m) {
+  if (csv) {
+    try {
+      const int rc0 = csv_listing(c, g, *csv, d_keys, d_koff, d_sizes, d_tiers, &m, s, msg);
+      if (rc0 != S3IMPH_OK) return rc0;
+    } catch (const Fail& f) {
+      throw Fail{f.code, "csv: " + f.msg};
+    }
+    out->m = m;
+    if (m == 0) return S3IMPH_OK;
+    const int rc0 = sort_listing(c, g, d_keys, d_koff, d_sizes, d_tiers, m, s, msg);
+    if (rc0 != S3IMPH_OK) return rc0;
+  } else if (m) {
+    out->m = m;
     upload_keys(c, g, keys, koff, m, d_keys, d_koff);
     if (sizes) {
       g.make(d_sizes, m);
@@ -992,7 +1008,12 @@ int s3imph_aggregate_tiers_host(int device, const uint8_t* keys, const uint64_t*
 // `unsorted` s3imph_index_from_unsorted_objects_host (s3imph_sort.hip).
 int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
                                const uint8_t* tiers, uint64_t m, uint32_t max_depth, const char* out_dir,
-                               bool unsorted, char* err, size_t errlen) {
+                               bool unsorted, char* err, size_t errlen, const CsvFiles* csv) {
+  static const uint8_t kWanted = 0;
+  if (csv) {
+    keys = nullptr, key_offsets = sizes = nullptr, m = 0;
+    tiers = csv->with_tiers ? &kWanted : nullptr;
+  }
   if (!out_dir || !listing_given(keys, key_offsets, m)) return S3IMPH_ERR_INVALID;
   const std::string dir = out_dir;
   if (!is_dir(dir)) {
@@ -1007,10 +1028,12 @@ int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* 
     std::vector<uint64_t> fp, pos, offs, send, dpos, doff, ocnt, tbytes, tcount, tcbytes;
     uint64_t present_mask = 0;
     std::vector<uint32_t> depth, maxds;
-    if (m) {
+    uint64_t csv_bytes = 0;
+    for (uint64_t i = 0; csv && i < csv->n_files; ++i) csv_bytes += csv->len[i];
+    if (m || csv_bytes) {
       s3imph_ctx* c = default_ctx(device, &msg);
       if (!c) {
-        set_err(err, errlen, "aggregate: " + msg);
+        set_err(err, errlen, (csv ? "csv: " : "aggregate: ") + msg);
         return S3IMPH_ERR_HIP;
       }
       std::lock_guard<std::mutex> lk(c->mu);
@@ -1020,9 +1043,10 @@ int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* 
       const int rc = retry_on_nomem(c, s, &msg, [&]() -> int {
         DevGuard g;
         DevRows r;
-        int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers, unsorted);
+        int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers, unsorted, csv);
         if (rc2 != S3IMPH_OK) return rc2;
         n = r.n;
+        if (r.m == 0) return S3IMPH_OK;  // CSV text without an object: the empty index below
         if (tiers) {  // the columns of the present tiers leave HBM before the build needs the room
           present_mask = r.present_mask;
           tcount.resize(kNT * n);
@@ -1087,7 +1111,8 @@ int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* 
         set_err(err, errlen, msg);
         return rc;
       }
-    } else {
+    }
+    if (n == 0) {
       offs = {0};
       doff = {0, 0};  // writeEmpty-like: maxDepth 0 -> offsets [0, 0]
     }
@@ -1102,7 +1127,9 @@ int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* 
     return rc;
   } catch (const Fail& f) {
     // a failure inside the sort stage comes worded "sort: ..." (rows_from_host)
-    set_err(err, errlen, f.msg.compare(0, 6, "sort: ") == 0 ? f.msg : "aggregate: " + f.msg);
+    // and one inside the CSV parse "csv: ..."
+    set_err(err, errlen,
+            f.msg.compare(0, 6, "sort: ") == 0 || f.msg.compare(0, 5, "csv: ") == 0 ? f.msg : "aggregate: " + f.msg);
     return f.code;
   } catch (const std::bad_alloc&) {
     set_err(err, errlen, "aggregate: out of host memory");

@@ -2340,15 +2340,17 @@ bool reclaim_cached(s3imph_ctx* keep, const void* keep_set) {
       fin_scratch_free(c);
       agg_scratch_free(c);
       sort_scratch_free(c);
+      csv_scratch_free(c);
       c->have_build = false;
       c->rank_valid = false;
       any = true;
     }
   }
-  if (keep && (keep->fin || keep->agg || keep->srt)) {
+  if (keep && (keep->fin || keep->agg || keep->srt || keep->csv)) {
     fin_scratch_free(keep);
     agg_scratch_free(keep);
     sort_scratch_free(keep);
+    csv_scratch_free(keep);
     any = true;
   }
   if (keep) (void)hipSetDevice(keep->device);
@@ -2929,6 +2931,7 @@ int s3imph_ctx_destroy(s3imph_ctx* c) {
   fin_scratch_free(c);
   agg_scratch_free(c);
   sort_scratch_free(c);
+  csv_scratch_free(c);
   if (c->d.xo) (void)hipStreamSynchronize(c->d.xo);
   delete c->d.xcomm;
   c->d.xcomm = nullptr;
@@ -3337,6 +3340,7 @@ int s3imph_release_workspaces(void) {
     fin_scratch_free(c);
     agg_scratch_free(c);
     sort_scratch_free(c);
+    csv_scratch_free(c);
     c->have_build = false;
     c->rank_valid = false;
   }

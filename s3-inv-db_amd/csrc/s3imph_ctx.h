@@ -235,6 +235,7 @@ namespace s3imph {
 struct FinScratch;  // s3imph_finalize.hip
 struct AggScratch;  // s3imph_aggregate.hip
 struct SortScratch;  // s3imph_sort.hip
+struct CsvScratch;  // s3imph_csv.hip
 }
 
 struct s3imph_ctx {
@@ -242,6 +243,7 @@ struct s3imph_ctx {
   s3imph::FinScratch* fin = nullptr;  // finalize-pass scratch (s3imph_finalize.hip), lazily made
   s3imph::AggScratch* agg = nullptr;  // aggregation scratch and the last plan (s3imph_aggregate.hip), lazily made
   s3imph::SortScratch* srt = nullptr;  // listing sort / gather scratch (s3imph_sort.hip), lazily made
+  s3imph::CsvScratch* csv = nullptr;  // CSV parse scratch and the last plan (s3imph_csv.hip), lazily made
   uint32_t* mid = nullptr;            // k_mid_levels scratch (kMidScratchU32), lazily made
   Rec* split = nullptr;               // k_tile_split scratch, made for sets big enough for 2^15+ tiles
   hipStream_t own_stream = nullptr;
@@ -404,9 +406,12 @@ void upload_keys(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t
 // Listing to directory (s3imph_aggregate.hip): the row path behind s3imph_index_from_objects[_tiers]_host
 // (tiers nullable); with `unsorted` the listing's device copy is sorted and gathered first
 // (s3imph_index_from_unsorted_objects_host).
+// With `csv` the listing is not given but parsed on the device from CSV buffers (s3imph_csv.hip;
+// s3imph_index_from_csv_host): keys, key_offsets, sizes, tiers and m are then ignored.
+struct CsvFiles;
 int index_from_objects(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
                        const uint8_t* tiers, uint64_t m, uint32_t max_depth, const char* out_dir, bool unsorted,
-                       char* err, size_t errlen);
+                       char* err, size_t errlen, const CsvFiles* csv = nullptr);
 // Listing sort (s3imph_sort.hip): the byte order of m object keys in HBM (order[j] = input index
 // of the j-th key, equal keys in input order; fills *info) and the out-of-place gather of the
 // listing into an order; both wait for the stream.
@@ -416,6 +421,28 @@ int gather_objects(s3imph_ctx* c, const uint8_t* keys, const uint64_t* koff, con
                    const uint8_t* tiers, uint64_t m, const uint32_t* order, uint8_t* keys_out, uint64_t keys_cap,
                    uint64_t* off_out, uint64_t* sizes_out, uint8_t* tiers_out, hipStream_t s, std::string* msg);
 void sort_scratch_free(s3imph_ctx* c);
+// Inventory CSV (s3imph_csv.hip).  A lane of the automaton passes walks a run of kCsvRunBytes, a
+// workgroup a tile of kCsvTileBytes (s3imph_csv_geometry tells the tests).  plan: every pass that
+// sizes the listing of one buffer in HBM (fills *info, keeps the plan); fill: the plan's listing,
+// its keys from byte key_base of `keys` on; both wait for the stream.
+constexpr int kCsvRunBytes = 32, kCsvTileBytes = 8192;
+int csv_plan(s3imph_ctx* c, const uint8_t* csv, uint64_t len, const s3imph_csv_schema& schema, s3imph_csv_info* info,
+             hipStream_t s, std::string* msg);
+int csv_fill(s3imph_ctx* c, uint8_t* keys, uint64_t keys_cap, uint64_t key_base, uint64_t* offsets, uint64_t* sizes,
+             uint8_t* tiers, hipStream_t s, std::string* msg);
+void csv_scratch_free(s3imph_ctx* c);
+// Host CSV buffers to one listing in HBM, file after file (owned by g; *m objects; *total sums
+// the files' infos when given).
+struct CsvFiles {
+  const uint8_t* const* csv;
+  const uint64_t* len;
+  uint64_t n_files;
+  const s3imph_csv_schema* schema;
+  bool with_tiers;
+  s3imph_csv_info* total;
+};
+int csv_listing(s3imph_ctx* c, DevGuard& g, const CsvFiles& f, uint8_t*& d_keys, uint64_t*& d_koff,
+                uint64_t*& d_sizes, uint8_t*& d_tiers, uint64_t* m, hipStream_t s, std::string* msg);
 // A context (s3imph_ctx_create) whose multi-GPU collectives go through `comm` (owned).
 s3imph_ctx* make_dist_ctx(int device, Comm* comm, int rank, int nranks, std::string* msg);
 

@@ -19,33 +19,18 @@ namespace {
 struct TierInfo {
   const char *name, *file;
 };
-// AllTiers, tiers.go:39-53
-const TierInfo kTiers[S3IMPH_NUM_TIERS] = {
-    {"STANDARD", "standard"},
-    {"STANDARD_IA", "standard_ia"},
-    {"ONEZONE_IA", "onezone_ia"},
-    {"GLACIER_IR", "glacier_ir"},
-    {"GLACIER", "glacier_fr"},
-    {"DEEP_ARCHIVE", "deep_archive"},
-    {"REDUCED_REDUNDANCY", "reduced_redundancy"},
-    {"INTELLIGENT_TIERING_FREQUENT", "it_frequent"},
-    {"INTELLIGENT_TIERING_INFREQUENT", "it_infrequent"},
-    {"INTELLIGENT_TIERING_ARCHIVE_INSTANT", "it_archive_instant"},
-    {"INTELLIGENT_TIERING_ARCHIVE", "it_archive"},
-    {"INTELLIGENT_TIERING_DEEP_ARCHIVE", "it_deep_archive"},
-};
+// AllTiers, tiers.go:39-53 (the table itself: s3imph_tiers.h)
+#define S3IMPH_TIER_ROW(id, name, file) {name, file},
+const TierInfo kTiers[S3IMPH_NUM_TIERS] = {S3IMPH_TIER_TABLE(S3IMPH_TIER_ROW)};
+#undef S3IMPH_TIER_ROW
 
-// strings.ToUpper(strings.TrimSpace(s)) for the ASCII names S3 uses (TrimSpace's ASCII set)
-std::string trim_upper(const char* s) {
+// strings.TrimSpace(s) by the shared rule (tier_space): the bytes left, any letter case
+std::string trimmed(const char* s) {
   std::string t = s ? s : "";
-  auto space = [](unsigned char ch) { return ch == ' ' || (ch >= '\t' && ch <= '\r'); };
   size_t b = 0, e = t.size();
-  while (b < e && space((unsigned char)t[b])) ++b;
-  while (e > b && space((unsigned char)t[e - 1])) --e;
-  t = t.substr(b, e - b);
-  for (char& ch : t)
-    if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 'a' + 'A');
-  return t;
+  while (b < e && tier_space((unsigned char)t[b])) ++b;
+  while (e > b && tier_space((unsigned char)t[e - 1])) --e;
+  return t.substr(b, e - b);
 }
 
 // A reader for tiers.json: any JSON value is accepted and skipped, the fields of
@@ -389,18 +374,9 @@ using namespace s3imph;
 extern "C" {
 
 int s3imph_tier_from_s3(const char* storage_class, const char* access_tier) {
-  const std::string sc = trim_upper(storage_class), at = trim_upper(access_tier);
-  if (sc == "INTELLIGENT_TIERING") {
-    if (at == "FREQUENT_ACCESS" || at == "FREQUENT") return S3IMPH_TIER_IT_FREQUENT;
-    if (at == "INFREQUENT_ACCESS" || at == "INFREQUENT") return S3IMPH_TIER_IT_INFREQUENT;
-    if (at == "ARCHIVE_INSTANT_ACCESS") return S3IMPH_TIER_IT_ARCHIVE_INSTANT;
-    if (at == "ARCHIVE_ACCESS" || at == "ARCHIVE") return S3IMPH_TIER_IT_ARCHIVE;
-    if (at == "DEEP_ARCHIVE_ACCESS" || at == "DEEP_ARCHIVE") return S3IMPH_TIER_IT_DEEP_ARCHIVE;
-    return S3IMPH_TIER_IT_FREQUENT;  // missing or unknown access tier
-  }
-  for (int t = 0; t < S3IMPH_NUM_TIERS; ++t)
-    if (sc == kTiers[t].name) return t;
-  return S3IMPH_TIER_STANDARD;  // unknown class
+  const std::string sc = trimmed(storage_class), at = trimmed(access_tier);
+  return tier_from_trimmed(reinterpret_cast<const unsigned char*>(sc.data()), (unsigned)std::min<size_t>(sc.size(), kTierNameMax + 1),
+                           reinterpret_cast<const unsigned char*>(at.data()), (unsigned)std::min<size_t>(at.size(), kTierNameMax + 1));
 }
 
 const char* s3imph_tier_name(int id) { return id >= 0 && id < S3IMPH_NUM_TIERS ? kTiers[id].name : nullptr; }

@@ -16,7 +16,8 @@ multi-GPU rank API (``DistBuilder``), the batched lookup (``MPHF``), the reader,
 of the pipeline: ``aggregate`` (extsort.Aggregator + SortPrefixRows: object listing -> prefix
 rows) and ``build_index_from_objects`` (object listing -> index directory), both for a
 byte-sorted listing; ``sort_objects`` and ``build_index_from_unsorted_objects`` take one in any
-order (the stable byte-order sort and the gather run on the GPU too).  With one tier id
+order (the stable byte-order sort and the gather run on the GPU too); ``parse_inventory_csv`` and
+``build_index_from_inventory_csv`` start from the inventory's CSV text.  With one tier id
 per object (``TIERS``, ``tier_from_s3``) both also carry the per-storage-class statistics that
 ``Index.tier_breakdown*`` answer from.
 
@@ -85,6 +86,8 @@ EXPORTS = (
     "s3imph_index_attach_tiers", "s3imph_index_tier_count", "s3imph_index_tier_ids", "s3imph_index_tiers_device",
     "s3imph_sort_objects_device", "s3imph_gather_objects_device", "s3imph_sort_objects_host",
     "s3imph_index_from_unsorted_objects_host",
+    "s3imph_csv_header_schema", "s3imph_csv_plan_device", "s3imph_csv_fill_device", "s3imph_csv_parse_host",
+    "s3imph_index_from_csv_host", "s3imph_csv_geometry",
 )
 NUM_TIERS = 12  # S3IMPH_NUM_TIERS
 
@@ -160,6 +163,23 @@ class SortInfo(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {f: getattr(self, f) for f, _ in self._fields_ if f != "pad"}
+
+
+class CsvSchema(ctypes.Structure):
+    """s3imph_csv_schema: the columns of an inventory CSV (include/s3imph.h, section 5g)."""
+    _fields_ = [("key_col", ctypes.c_int32), ("size_col", ctypes.c_int32), ("storage_col", ctypes.c_int32),
+                ("access_tier_col", ctypes.c_int32)]
+
+
+class CsvInfo(ctypes.Structure):
+    """s3imph_csv_info: what a CSV parse found (include/s3imph.h, section 5g)."""
+    _fields_ = [
+        ("n_records", ctypes.c_uint64), ("n_objects", ctypes.c_uint64), ("key_bytes", ctypes.c_uint64),
+        ("n_short", ctypes.c_uint64), ("n_empty_key", ctypes.c_uint64), ("n_bad_size", ctypes.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 # s3imph_node: what Index.nodes returns, one record per queried position
@@ -253,6 +273,13 @@ def _load():
         "s3imph_gather_objects_device": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]),
         "s3imph_sort_objects_host": (i32, [i32, vp, vp, u64, P(vp), P(SortInfo), cp, sz]),
         "s3imph_index_from_unsorted_objects_host": (i32, [i32, vp, vp, vp, vp, u64, ctypes.c_uint32, cp, cp, sz]),
+        "s3imph_csv_header_schema": (i32, [vp, u64, P(CsvSchema), P(u64), cp, sz]),
+        "s3imph_csv_plan_device": (i32, [vp, vp, u64, P(CsvSchema), P(CsvInfo), vp]),
+        "s3imph_csv_fill_device": (i32, [vp, vp, u64, u64, vp, vp, vp, vp]),
+        "s3imph_csv_parse_host": (i32, [i32, vp, u64, P(CsvSchema), P(vp), P(vp), P(vp), P(vp), P(CsvInfo), cp, sz]),
+        "s3imph_index_from_csv_host": (i32, [i32, P(vp), P(u64), u64, P(CsvSchema), i32, ctypes.c_uint32, cp,
+                                             P(CsvInfo), cp, sz]),
+        "s3imph_csv_geometry": (None, [P(ctypes.c_uint32), P(ctypes.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -691,6 +718,47 @@ class DeviceBuilder:
         return {"keys": keys[: (nbytes + 7) // 8 * 8], "offsets": offs, "sizes": None if sizes is None else sizes[:m],
                 "tiers": None if tiers is None else tiers[:m], "key_bytes": nbytes}
 
+    def csv_plan(self, d_csv, length: int, schema, stream=None) -> dict:
+        """s3imph_csv_plan_device: every pass that sizes the listing of one inventory CSV buffer in
+        HBM (d_csv: a uint8 tensor or an address, any alignment, readable to round_up(length, 8)).
+        schema = (key_col, size_col, storage_col, access_tier_col).  Returns s3imph_csv_info as a
+        dict and keeps the plan for csv_fill."""
+        info = CsvInfo()
+        rc = LIB.s3imph_csv_plan_device(self._h, _dev_ptr(d_csv), length, ctypes.byref(_csv_schema(schema)),
+                                        ctypes.byref(info), _stream_ptr(stream))
+        self.last_csv = info.as_dict()
+        if rc != OK:
+            e = MPHFError(rc, self.last_error() or f"csv: {status_string(rc)}")
+            e.info = self.last_csv
+            raise e
+        return self.last_csv
+
+    def csv_fill(self, d_keys=None, d_key_offsets=None, d_sizes=None, d_tiers=None, key_base: int = 0,
+                 keys_cap: int | None = None, with_tiers: bool = True, stream=None) -> dict:
+        """s3imph_csv_fill_device: the last csv_plan's listing as torch tensors: keys (uint8),
+        offsets (int64, n_objects + 1, starting at key_base), sizes (int64 holding the u64 bits),
+        tiers (uint8, or None without with_tiers).  Without arguments the arrays are made here, the
+        keys padded to 8 bytes; given arrays are written in place (key_base: where the keys start in
+        d_keys; keys_cap defaults to its length), so file after file appends into one listing."""
+        import torch
+        info = getattr(self, "last_csv", None) or {"n_objects": 0, "key_bytes": 0}
+        n, end = info["n_objects"], key_base + info["key_bytes"]
+        dev = f"cuda:{self.device}"
+        keys = torch.empty(max((end + 7) // 8 * 8, 8), dtype=torch.uint8, device=dev) if d_keys is None else d_keys
+        if keys_cap is None:
+            keys_cap = (end + 7) // 8 * 8 if d_keys is None else int(d_keys.numel())
+        offs = torch.empty(n + 1, dtype=torch.int64, device=dev) if d_key_offsets is None else d_key_offsets
+        sizes = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if d_sizes is None else d_sizes
+        tiers = d_tiers
+        if tiers is None and with_tiers:
+            tiers = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        rc = LIB.s3imph_csv_fill_device(self._h, _dev_ptr(keys), keys_cap, key_base, _dev_ptr(offs), _dev_ptr(sizes),
+                                        _dev_ptr(tiers), _stream_ptr(stream))
+        if rc != OK:
+            raise MPHFError(rc, self.last_error() or f"csv: {status_string(rc)}")
+        return {"keys": keys[: (end + 7) // 8 * 8] if d_keys is None else keys, "offsets": offs[: n + 1],
+                "sizes": sizes[:n], "tiers": None if tiers is None else tiers[:n], "key_bytes": info["key_bytes"]}
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             LIB.s3imph_ctx_destroy(self._h)
@@ -818,6 +886,78 @@ def build_index_from_unsorted_objects(keys_blob: np.ndarray, key_offsets: np.nda
     err = ctypes.create_string_buffer(1024)
     _check(LIB.s3imph_index_from_unsorted_objects_host(device, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), _np_ptr(tr),
                                                        m, max_depth, os.fsencode(out_dir), err, 1024), err)
+
+
+def _csv_schema(schema) -> CsvSchema:
+    if isinstance(schema, CsvSchema):
+        return schema
+    cols = tuple(int(c) for c in schema) + (-1, -1)
+    return CsvSchema(*cols[:4])
+
+
+def csv_geometry() -> tuple[int, int]:
+    """(run bytes, tile bytes) of the CSV automaton passes: a lane walks a run, a workgroup a tile
+    (s3imph_csv_geometry; for tests that place events on the edges)."""
+    run, tile = ctypes.c_uint32(), ctypes.c_uint32()
+    LIB.s3imph_csv_geometry(ctypes.byref(run), ctypes.byref(tile))
+    return int(run.value), int(tile.value)
+
+
+def csv_header_schema(data) -> tuple[tuple[int, int, int, int], int]:
+    """s3imph_csv_header_schema (OpenFileWithOptions, reader.go:96-135; host only): the columns
+    named key / size / storageclass / intelligenttieringaccesstier in the CSV's first record
+    (-1: absent) and the byte offset where the data rows begin."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    sch, start = CsvSchema(), ctypes.c_uint64()
+    err = ctypes.create_string_buffer(1024)
+    _check(LIB.s3imph_csv_header_schema(_np_ptr(buf), len(buf), ctypes.byref(sch), ctypes.byref(start), err, 1024), err)
+    return (sch.key_col, sch.size_col, sch.storage_col, sch.access_tier_col), int(start.value)
+
+
+def parse_inventory_csv(data, schema, device: int = 0):
+    """s3imph_csv_parse_host: decompressed inventory CSV bytes -> the object listing CSVReader.Read
+    (reader.go:250-297) returns record by record, parsed on the GPU: (keys_blob u8, key_offsets
+    u64[m + 1], sizes u64[m], tiers u8[m], info dict).  schema = (key_col, size_col, storage_col,
+    access_tier_col), the last two -1 when absent."""
+    buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8)
+    out = [ctypes.c_void_p() for _ in range(4)]
+    info = CsvInfo()
+    err = ctypes.create_string_buffer(1024)
+    rc = LIB.s3imph_csv_parse_host(device, _np_ptr(buf), len(buf), ctypes.byref(_csv_schema(schema)),
+                                   *[ctypes.byref(p) for p in out], ctypes.byref(info), err, 1024)
+    try:
+        _check(rc, err)
+
+        def take(p, dtype, count):
+            a = np.zeros(count, dtype)
+            if count and p.value:
+                ctypes.memmove(a.ctypes.data, p.value, a.nbytes)
+            return a
+
+        m = info.n_objects
+        return (take(out[0], np.uint8, info.key_bytes), take(out[1], np.uint64, m + 1), take(out[2], np.uint64, m),
+                take(out[3], np.uint8, m), info.as_dict())
+    finally:
+        for p in out:
+            if p.value:
+                LIB.s3imph_free(p)
+
+
+def build_index_from_inventory_csv(files, schema, out_dir: str, with_tiers: bool = False, max_depth: int = 0,
+                                   device: int = 0) -> dict:
+    """s3imph_index_from_csv_host: decompressed inventory CSV buffers (a list of bytes-likes, each
+    parsed on its own and appended in order) -> index directory, everything after the H2D on the
+    GPU: parse, sort, aggregation, MPHF build, finalize.  Returns the summed s3imph_csv_info."""
+    bufs = [np.frombuffer(bytes(f), np.uint8) if not isinstance(f, np.ndarray) else np.ascontiguousarray(f, np.uint8)
+            for f in files]
+    k = len(bufs)
+    ptrs = (ctypes.c_void_p * max(k, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    lens = (ctypes.c_uint64 * max(k, 1))(*[b.size for b in bufs])
+    info = CsvInfo()
+    err = ctypes.create_string_buffer(1024)
+    _check(LIB.s3imph_index_from_csv_host(device, ptrs, lens, k, ctypes.byref(_csv_schema(schema)), int(with_tiers),
+                                          max_depth, os.fsencode(out_dir), ctypes.byref(info), err, 1024), err)
+    return info.as_dict()
 
 
 def write_manifest(out_dir: str, node_count: int, max_depth: int) -> None:
