@@ -6,6 +6,7 @@ no comment character and TrimLeadingSpace = false, and the reader's rules on top
   parse_lines(data)      the line-based form, readLine + readRecord as encoding/csv writes them:
                          what the GPU is compared with (a different formulation from its kernels);
   parse_automaton(data)  the five-state byte automaton of the header, a second statement;
+  state_at(data, offs)   that automaton's state just before given offsets (for generated inputs);
   records(data, schema)  CSVReader.Read's rules (pkg/inventory/reader.go:250-297) over parse_lines.
 
 Go is not on the build machine: both rest on a reading of encoding/csv, and agree with each other
@@ -122,17 +123,26 @@ def parse_lines(data: bytes, trace=None) -> list:
 R, F, U, Q, E = range(5)
 
 
-def parse_automaton(data: bytes, with_ends: bool = False):
+def _automaton(data: bytes, probes=()):
+    """The one loop behind parse_automaton and state_at: (records, record ends, the state just
+    before each offset of `probes`, which must ascend; an offset of len(data) is the final state)."""
     data = bytes(data)
     n = len(data)
     out, ends, fields, cur = [], [], [], bytearray()
     st = R
+    seen = []
+    probes = list(probes)
+    assert probes == sorted(probes) and all(0 <= p <= n for p in probes)
+    nxt = probes[0] if probes else -1
 
     def end_field():
         fields.append(bytes(cur))
         cur.clear()
 
     for i, c in enumerate(data):
+        while i == nxt:
+            seen.append(st)
+            nxt = probes[len(seen)] if len(seen) < len(probes) else -1
         if c == 0x0D and (i + 1 == n or data[i + 1] == 0x0A):
             continue
         quote, comma, nl = c == 0x22, c == 0x2C, c == 0x0A
@@ -166,11 +176,30 @@ def parse_automaton(data: bytes, with_ends: bool = False):
         else:
             cur.append(c)
             st = U
+    seen += [st] * (len(probes) - len(seen))  # probes at len(data)
     if st != R:
         end_field()
         out.append(fields)
         ends.append(n)
+    return out, ends, seen
+
+
+def parse_automaton(data: bytes, with_ends: bool = False):
+    out, ends, _ = _automaton(data)
     return (out, ends) if with_ends else out
+
+
+def state_at(data: bytes, offsets) -> list:
+    """The automaton's state just before each byte offset (a deleted '\\r' leaves it as it is; at
+    len(data): the state in which the buffer ends), in the order given.  For tests that must prove
+    that a generated input puts what it claims where it claims."""
+    offsets = list(offsets)
+    order = sorted(range(len(offsets)), key=offsets.__getitem__)
+    seen = _automaton(data, [offsets[j] for j in order])[2]
+    got = [None] * len(offsets)
+    for j, s in zip(order, seen):
+        got[j] = s
+    return got
 
 
 # ----------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import random
 import numpy as np
 import pytest
 
+import csv_cases as K
 import csv_ref as C
 import oracle as O
 import s3imph
@@ -166,6 +167,74 @@ def test_a_quoted_field_open_across_three_tiles(ctx):
     assert want["keys"][-1] == b"last" and want["sizes"].tolist()[-2:] == [77, 1]
 
 
+@pytest.mark.parametrize("edge", [RUN, TILE, 2 * TILE], ids=["run", "tile", "second_tile"])
+def test_every_state_before_every_kind_of_byte_at_an_edge(ctx, edge):
+    """csv_cases.matrix: each of the five states just before the edge, each of the eight things
+    that can stand there (test_csv_ref.py proves the texts are what they claim)."""
+    objects = 0
+    for name, state, at, text in K.matrix(edge):
+        try:
+            objects += check(ctx, text)["info"]["n_objects"]
+        except AssertionError as e:
+            raise AssertionError("%s at %d: %s" % (name, at, e)) from e
+    assert objects > 55 * (edge // len(K.ROW) - 2)
+
+
+# ---------------------------------------------------------------------------------------------
+# more tiles than k_csv_tile_scan has lanes: a lane composes and walks a share of several tiles
+# ---------------------------------------------------------------------------------------------
+def test_scan_edges_the_matrix_at_lane_boundaries_of_the_tile_scan(ctx):
+    text, placed = K.scan_edges()
+    assert len(text) == 1024 * TILE + 1 and len(placed) == 80
+    want = check(ctx, text)
+    assert want["info"]["n_objects"] > 80000
+
+
+def test_short_rows_in_1024_and_1025_tiles(ctx):
+    """Every lane of the tile scan busy with one tile; then shares of two, the last busy lane with
+    one tile and the lanes behind it idle.  About 1.9e5 records and 3.9 MB of keys through the
+    record scans, k_csv_meta and the key fill."""
+    text = filler(1024 * TILE + 1)
+    want = check(ctx, text[:1024 * TILE], (0, 1, 2, 3))
+    assert want["info"]["n_objects"] > 150000 and want["info"]["key_bytes"] > 3 * 10**6
+    check(ctx, text, (0, 1, 2, 3))
+
+
+def test_long_rows_three_tiles_per_lane_then_small_plans_on_the_same_scratch(ctx):
+    text = K.long_rows()
+    assert len(text) == 2048 * TILE + 1
+    want = check(ctx, text, (0, 1, 2, 3))
+    assert want["info"]["n_objects"] > 20000 and want["info"]["key_bytes"] > 14 * 10**6
+    # the scratch of 2049 tiles and its record arrays stay in the context: a plan of one tile and
+    # one of three must not read what the large one left past their own tiles and records
+    check(ctx, b"k,5\n")
+    check(ctx, filler(2 * TILE + 100, seed=21), (0, 1, 2, 3))
+
+
+# ---------------------------------------------------------------------------------------------
+# size fields
+# ---------------------------------------------------------------------------------------------
+def test_size_fields_on_the_device(ctx):
+    text, want = K.sizes_text()
+    ref = check(ctx, text)
+    assert ref["sizes"].tolist() == [v for _, v, _ in want]
+    assert ref["info"]["n_bad_size"] == sum(not ok for _, _, ok in want) > 40
+
+
+def test_size_literals_on_the_device(ctx):
+    """Literals straight from the device's arrays, so that the reference and the device cannot be
+    wrong together."""
+    rows = [(b"18446744073709551615", 2**64 - 1), (b"18446744073709551616", 0), (b"18446744073709551621", 0),
+            (b"+1", 0), (b"0" * 30 + b"5", 5), (b"18446744073709551609", 2**64 - 7), (b"1844674407370955162", 1844674407370955162),
+            (b'"\v\f\r\n7 "', 7), (b"99999999999999999999", 0), (b"9223372036854775808", 2**63)]
+    text = b"".join(b"k%d,%s\n" % (i, t) for i, (t, _) in enumerate(rows))
+    d_csv = to_dev(text)  # the plan keeps its address until the fill
+    info = ctx.csv_plan(d_csv, len(text), KS)
+    assert info["n_objects"] == info["n_records"] == len(rows) and info["n_bad_size"] == 4
+    out = ctx.csv_fill(with_tiers=False)
+    assert out["sizes"].cpu().numpy().view(np.uint64).tolist() == [v for _, v in rows]
+
+
 # ---------------------------------------------------------------------------------------------
 # degenerate inputs
 # ---------------------------------------------------------------------------------------------
@@ -213,28 +282,39 @@ def test_one_record_longer_than_two_tiles(ctx):
 # ---------------------------------------------------------------------------------------------
 def fuzz_inputs(count=300, seed=9157):
     rng = random.Random(seed)
-    alphabet = b'",\n\ra 1/\x80'
-    tokens = [b",", b",", b"\n", b"\r\n", b'"', b'""', b"a/b", b"17", b" 5 ", b"GLACIER", b"x\x80y", b"\r", b' "q" ',
-              b"STANDARD_IA", b"intelligent_tiering", b"ARCHIVE"]
     out = []
     for i in range(count):
         n = rng.randrange(0, 4097) if i % 10 else rng.choice([0, 1, 2, 4095, 4096])
-        if i % 2:
-            d = bytes(rng.choice(alphabet) for _ in range(n))
-        else:
-            d = bytearray()
-            while len(d) < n:
-                d += rng.choice(tokens)
-            d = bytes(d[:n])
-        out.append(d)
+        out.append(K.fuzz_text(rng, n, i % 2 == 1))
     return out
 
 
+def fuzz_inputs_over_a_tile_edge(count=60, seed=8192):
+    """The same two generators at lengths of one to two tiles: whatever they make stands at the
+    tile edge, and the text ends anywhere from just before the first edge to just past the second."""
+    rng = random.Random(seed)
+    ends = [TILE - 64, TILE - 1, TILE, TILE + 1, 2 * TILE - 1, 2 * TILE, 2 * TILE + 1, 2 * TILE + 64]
+    return [K.fuzz_text(rng, rng.randrange(TILE - 64, 2 * TILE + 65) if i % 5 else rng.choice(ends), i % 2 == 1)
+            for i in range(count)]
+
+
+FUZZ_SCHEMAS = [(0, 1, 2, 3), (1, 0, 5, 2)]  # key_col > size_col; storage_col beyond most records
+
+
 def test_fuzz(ctx):
-    schemas = [(0, 1, 2, 3), (1, 0, 5, 2)]  # key_col > size_col; storage_col beyond most records
     kept = 0
     for i, d in enumerate(fuzz_inputs()):
-        kept += check(ctx, d, schemas[i % 2])["info"]["n_objects"]
+        kept += check(ctx, d, FUZZ_SCHEMAS[i % 2])["info"]["n_objects"]
+    assert kept > 1000
+
+
+def test_fuzz_over_a_tile_edge(ctx):
+    inputs = fuzz_inputs_over_a_tile_edge()
+    assert len(inputs) == 60 and all(TILE - 64 <= len(d) <= 2 * TILE + 64 for d in inputs)
+    kept = 0
+    for i, d in enumerate(inputs):
+        # both generators under both schemas: the generator alternates with i, the schema with i // 2
+        kept += check(ctx, d, FUZZ_SCHEMAS[i // 2 % 2])["info"]["n_objects"]
     assert kept > 1000
 
 
@@ -277,6 +357,44 @@ def test_append_two_buffers_into_one_listing(ctx, out_align):
     assert d_offs.cpu().numpy().view(np.uint64).tolist() == offs1.tolist() + offs2.tolist()[1:] + [2**64 - 1]
     assert d_sizes.cpu().numpy().view(np.uint64).tolist() == a["sizes"].tolist() + b["sizes"].tolist()
     assert d_tiers.cpu().numpy().tolist() == a["tiers"].tolist() + b["tiers"].tolist()
+
+
+@pytest.mark.parametrize("residue", range(8))
+def test_append_at_every_residue_of_key_base(ctx, residue):
+    """The second buffer's keys start `residue` bytes into an 8-byte word of the blob: the bytes
+    of that word below key_base survive the second fill, zeros pad the end, the poison stays."""
+    import torch
+    schema = (0, 1, 2, 3)
+    first = b"first/" + b"f" * ((residue - 16) % 8) + b",1,GLACIER\nsecond/one,2\n"
+    # a key that is written by the re-walk first, then one straight from the text, then many
+    second = b'"re""walk",3\nplain,4\n' + filler(RUN * 9 + residue, seed=30 + residue)
+    a, b = C.records(first, schema), C.records(second, schema)
+    n1, n2 = len(a["keys"]), len(b["keys"])
+    blob1, offs1 = C.listing(a)
+    kb = int(offs1[-1])
+    assert kb % 8 == residue and n1 == 2 and b["keys"][:2] == [b're"walk', b"plain"] and n2 > 5
+    blob2, offs2 = C.listing(b, key_base=kb)
+    total = (kb + b["info"]["key_bytes"] + 7) // 8 * 8
+    for out_align in (0, 5):
+        raw = torch.full((out_align + total + 16,), 0x5A, dtype=torch.uint8, device="cuda")
+        d_keys = raw[out_align:]
+        d_offs = torch.full((n1 + n2 + 2,), -1, dtype=torch.int64, device="cuda")
+        d_sizes = torch.full((n1 + n2 + 1,), -1, dtype=torch.int64, device="cuda")
+        d_tiers = torch.full((n1 + n2 + 1,), 0xEE, dtype=torch.uint8, device="cuda")
+        d_first, d_second = to_dev(first), to_dev(second)
+        assert ctx.csv_plan(d_first, len(first), schema) == a["info"]
+        ctx.csv_fill(d_keys, d_offs, d_sizes, d_tiers, keys_cap=total)
+        got = raw.cpu().numpy().tobytes()
+        assert got[out_align:out_align + len(blob1)] == blob1 and set(got[out_align + len(blob1):]) == {0x5A}
+        assert ctx.csv_plan(d_second, len(second), schema) == b["info"]
+        ctx.csv_fill(d_keys, d_offs[n1:], d_sizes[n1:], d_tiers[n1:], key_base=kb, keys_cap=total)
+        got = raw.cpu().numpy().tobytes()
+        assert got[:out_align] == b"\x5a" * out_align and got[out_align + total:] == b"\x5a" * 16
+        assert got[out_align:out_align + kb] == blob1[:kb]  # the first buffer's keys, those of the shared word too
+        assert got[out_align + kb:out_align + total] == blob2 and blob2.endswith(b"\0" * (-(kb + b["info"]["key_bytes"]) % 8))
+        assert d_offs.cpu().numpy().view(np.uint64).tolist() == offs1.tolist() + offs2.tolist()[1:] + [2**64 - 1]
+        assert d_sizes.cpu().numpy().view(np.uint64).tolist() == a["sizes"].tolist() + b["sizes"].tolist() + [2**64 - 1]
+        assert d_tiers.cpu().numpy().tolist() == a["tiers"].tolist() + b["tiers"].tolist() + [0xEE]
 
 
 def test_every_tier_name_on_the_device(ctx):
@@ -418,6 +536,44 @@ def test_directory_from_csv_equals_the_one_from_the_listing(tmp_path, case, eol)
     names = files_of(want)
     assert files_of(got) == names and "manifest.json" in names
     assert any(n.startswith("tier_stats") for n in names) == (tiers is not None and len(keys) > 0)
+    for n in names:
+        if n != "manifest.json":
+            assert (got / n).read_bytes() == (want / n).read_bytes(), n
+    a, b = s3imph.read_manifest(str(got)), s3imph.read_manifest(str(want))
+    a.pop("created_at")
+    b.pop("created_at")
+    assert a == b
+    s3imph.verify_manifest(str(got))
+
+
+@pytest.mark.parametrize("with_tiers", [False, True], ids=["plain", "tiers"])
+@pytest.mark.parametrize("kind", ["objects", "key_bytes"])
+def test_the_appended_listing_grows(tmp_path, kind, with_tiers):
+    """csv_listing sizes its arrays from the first file that yields an object; here later files
+    yield far more objects (kind "objects": after an empty file, one without an object and a sparse
+    one) or far more key bytes at fewer objects than estimated (kind "key_bytes"), so the arrays
+    are made anew and copied more than once with files already in them."""
+    files = K.growth_files(kind)
+    schema = (0, 1, 2, 3)
+    g = K.growth_estimate(files, schema)  # the preconditions, as test_csv_ref.py holds them
+    if kind == "objects":
+        assert g["objects"] > 2.25 * g["est_objects"]
+    else:
+        assert g["key_bytes"] > 2.25 * g["est_key_bytes"] and g["objects"] <= int(g["est_objects"])
+    ref = C.records(b"".join(files), schema)
+    each = [C.records(f, schema) for f in files]  # every file is parsed on its own: here that is the same
+    assert ref["keys"] == [k for r in each for k in r["keys"]] and len(set(ref["keys"])) == len(ref["keys"])
+    assert set(ref["tiers"].tolist()) >= ({0, 4, 5} if kind == "objects" else {2, 3})
+    got, want = tmp_path / "got", tmp_path / "want"
+    got.mkdir()
+    want.mkdir()
+    total = s3imph.build_index_from_inventory_csv(files, schema, str(got), with_tiers=with_tiers)
+    assert total == {k: sum(r["info"][k] for r in each) for k in ref["info"]}
+    blob, offs = O.keys_to_blob(ref["keys"])
+    s3imph.build_index_from_unsorted_objects(blob, offs, ref["sizes"], str(want), tiers=ref["tiers"] if with_tiers else None)
+    names = files_of(want)
+    assert files_of(got) == names and "manifest.json" in names
+    assert any(n.startswith("tier_stats") for n in names) == with_tiers
     for n in names:
         if n != "manifest.json":
             assert (got / n).read_bytes() == (want / n).read_bytes(), n
