@@ -811,6 +811,100 @@ int s3imph_index_from_csv_host(int device, const uint8_t *const *csv, const uint
 void s3imph_csv_geometry(uint32_t *run_bytes, uint32_t *tile_bytes);
 
 /* ------------------------------------------------------------------------
+ * 5h. The monthly storage cost of a position, and descendant rows ranked by it: what the
+ *     reference's `query --estimate-cost` does with an opened index — TierBreakdown(pos) fed into
+ *     pricing.ComputeMonthlyCost (internal/cli/cli.go:227-296, pkg/pricing/pricing.go:159-240) —
+ *     for a batch of positions on the GPU, and on top of it the rows of a descendants plan
+ *     (section 5c) cut to their k largest by cost, bytes or object count.
+ *
+ *     The rule per tier slot (id, count, bytes) of a breakdown, restating ComputeMonthlyCost.  All
+ *     floating point is IEEE binary64 in exactly this operation order, u64 -> f64 rounds to nearest,
+ *     u64(x) truncates toward zero, every u64 sum and product wraps:
+ *       an unpriced tier (bit id of priced_mask clear) is skipped;
+ *       storage = u64((f64(bytes) / 2^30) * price * 1e6);
+ *       avg = count ? bytes / count : 0;
+ *       id in {STANDARD_IA, ONEZONE_IA, GLACIER_IR} and 0 < avg < 131072:
+ *         penalty = u64((f64((131072 - avg) * count) / 2^30) * price * 1e6);
+ *       id one of the five IT_* and monitoring_per_1000_objects > 0:
+ *         mon = avg >= 131072 ? count : (avg > 0 ? count / 2 : 0);
+ *         mon > 0: monitoring += u64(f64(mon) / 1000.0 * monitoring_per_1000_objects * 1e6);
+ *       id in {GLACIER_FR, DEEP_ARCHIVE, IT_ARCHIVE, IT_DEEP_ARCHIVE} and count > 0:
+ *         overhead = u64((f64(count * 32768) / 2^30) * price * 1e6)
+ *                  + u64((f64(count * 8192) / 2^30) * standard_price_per_gb * 1e6);
+ *       per_tier[id] = storage + penalty + overhead; total += per_tier[id];
+ *     and at the end total += monitoring.  The host entry point and the kernel share one inline
+ *     function for this (csrc/s3imph_pricing.h).
+ *
+ *     Differences from the reference, deliberate:
+ *       - a double that is NaN or >= 2^64 converts to UINT64_MAX (Go leaves that conversion to the
+ *         implementation);
+ *       - a table with a negative, NaN or infinite price, fee or standard price is
+ *         S3IMPH_ERR_INVALID ("pricing: ..."), refused before any device work; the loader refuses a
+ *         negative value as S3IMPH_ERR_FORMAT;
+ *       - tiers are keyed by id: PerGBMonth's name of id t is s3imph_tier_name(t); names in a
+ *         price file that are none of the twelve are ignored (no breakdown can carry them);
+ *       - a table without a priced tier is saved with "per_gb_month": {} (Go writes null for a
+ *         nil map and {} for an empty one; the struct does not tell them apart).
+ * ------------------------------------------------------------------------ */
+typedef struct s3imph_price_table {
+    double   per_gb_month[S3IMPH_NUM_TIERS];   /* by tier id */
+    uint32_t priced_mask, pad;                 /* bit t: PerGBMonth has that name */
+    double   monitoring_per_1000_objects, standard_price_per_gb;
+} s3imph_price_table;                          /* 120 bytes */
+
+typedef struct s3imph_cost {
+    uint64_t total, monitoring, min_object_size, glacier_overhead;  /* CostResult's four, microdollars */
+    uint64_t per_tier[S3IMPH_NUM_TIERS];       /* PerTierMicrodollars by tier id, 0 where absent */
+    uint32_t tier_mask;                        /* bit t: the map has the key = tier t is priced AND in TierBreakdown(pos) (count | bytes != 0) */
+    uint32_t found;                            /* pos < Count() */
+} s3imph_cost;                                 /* 136 bytes */
+
+/* DefaultUSEast1Prices (pricing.go:67-93). */
+int s3imph_price_table_default(s3imph_price_table *pt);
+/* LoadPriceTable (pricing.go:96-108), host only.  Field names match without regard to case, map
+ * keys exactly; missing fields are 0 / empty, unknown fields are skipped.  A missing file is
+ * S3IMPH_ERR_IO ("read price table: ..."); malformed or wrongly shaped JSON, a number outside
+ * double's range or a negative value is S3IMPH_ERR_FORMAT ("parse price table: ..."). */
+int s3imph_price_table_load(const char *path, s3imph_price_table *pt, char *err, size_t errlen);
+/* SavePriceTable (pricing.go:111-122): the text json.MarshalIndent(pt, "", "  ") writes —
+ * per_gb_month (the priced tiers, keys in byte order), monitoring_per_1000_objects,
+ * standard_price_per_gb; numbers in shortest round-trip form, plain notation for decimal
+ * exponents in [-6, 21), else Go's e form; no trailing newline; mode 0644. */
+int s3imph_price_table_save(const char *path, const s3imph_price_table *pt, char *err, size_t errlen);
+/* ComputeMonthlyCost over a TierBreakdownAll-shaped input (T slots: ids, count, bytes), host only;
+ * found = 1.  S3IMPH_ERR_INVALID for T > 12, an id >= 12, a duplicate id or a refused table. */
+int s3imph_compute_monthly_cost(const uint8_t *ids, const uint64_t *count, const uint64_t *bytes, uint64_t T,
+                                const s3imph_price_table *pt, s3imph_cost *out);
+/* The batched TierBreakdown(pos) -> ComputeMonthlyCost: one record per position into d_out (nq
+ * entries, 8-byte aligned).  pos >= Count() (the UINT64_MAX of a failed lookup included) gives an
+ * all-zero record; an index without tier data gives S3IMPH_OK and records that are zero apart
+ * from `found`; nq == 0 is OK and touches nothing.  d_qpos may be the d_out of
+ * s3imph_index_descendants_fill.  s3imph_index_lookup_device followed by this is `query
+ * --estimate-cost` for a batch.  The table travels as a kernel argument.  More than 2^31 - 1
+ * workgroups of queries in one batch is S3IMPH_ERR_INVALID.  Synchronous on `stream`. */
+int s3imph_index_cost_device(s3imph_index *idx, const uint64_t *d_qpos, uint64_t nq, const s3imph_price_table *pt,
+                             s3imph_cost *d_out, void *stream);
+
+/* The rows of the last s3imph_index_descendants_plan (AT or UPTO, with its filter if it had one),
+ * each cut to its k largest positions by `key` — an extension over the reference, whose Filtered
+ * form only thresholds.  top_n[r] = min(k, len(row r)); entries [r * k, r * k + top_n[r]) of
+ * d_top_pos / d_top_key hold the row's positions with the largest keys and those keys, in
+ * descending key order as unsigned 64-bit, equal keys by ascending position; the remaining entries
+ * of the row are pos = UINT64_MAX, key = 0.  The plan stays, so a fill may still follow.
+ * S3IMPH_ERR_STATE without a plan, for COUNT / BYTES on an index without the two stats arrays and
+ * for COST without tier data; S3IMPH_ERR_INVALID for k == 0, an unknown key, a NULL or refused
+ * table with COST, n_rows * k >= 2^31 or a plan of 2^32 positions or more.  A plan with n_rows ==
+ * 0 or total == 0 is OK and writes only the padding and top_n.  The scratch (32 bytes per planned
+ * position plus the segmented sort's temporary) lives in the handle, grows on demand and is freed
+ * on close.  Synchronous on `stream`. */
+#define S3IMPH_RANK_OBJECT_COUNT 0
+#define S3IMPH_RANK_TOTAL_BYTES  1
+#define S3IMPH_RANK_MONTHLY_COST 2   /* s3imph_cost.total of the position */
+int s3imph_index_descendants_top(s3imph_index *idx, int key, const s3imph_price_table *pt /* COST only */,
+                                 uint32_t k, uint64_t *d_top_pos /* n_rows * k */, uint64_t *d_top_key /* n_rows * k */,
+                                 uint32_t *d_top_n /* n_rows */, void *stream);
+
+/* ------------------------------------------------------------------------
  * 6. Deterministic synthetic prefix sets (bench/test support, not on the path).
  *    kind: 0 = s3-like, lengths uniform in [max(10, avg/2), 3avg/2],
  *              distinct and byte-sorted;

@@ -9,7 +9,10 @@
 //   DescendantsAtDepth[Filtered] / DescendantsUpToDepth   index.go:206-297, over
 //   GetPositionsInSubtree (depthindex.go:193-259, two binary searches in a depth's slice);
 //   HasTierData / TierBreakdown / TierBreakdownAll / TierBreakdownForPrefix   index.go:360-399,
-//   over OpenTierStats / GetBreakdown[All] (tierstats.go:108-215; include/s3imph.h section 5e).
+//   over OpenTierStats / GetBreakdown[All] (tierstats.go:108-215; include/s3imph.h section 5e);
+//   query --estimate-cost: TierBreakdown(pos) -> pricing.ComputeMonthlyCost (internal/cli/cli.go:
+//   227-296, pkg/pricing/pricing.go:159-240; include/s3imph.h section 5h), and the plan's rows
+//   ranked by it (an extension: stable segmented sort of the filled rows, first k of each kept).
 //
 // GPU formulation.  A batch of descendants queries is a CSR: `levels` per query, `row_ptr`
 // over the result rows, and the flat list of positions.  The plan step runs one lane per
@@ -30,6 +33,8 @@
 
 #include "s3imph_ctx.h"
 #include "s3imph_keys.h"
+#include "s3imph_pricing.h"
+#include "s3imph_prim.h"
 #include "s3imph_tiers.h"
 
 namespace s3imph {
@@ -117,6 +122,91 @@ __global__ __launch_bounds__(kQT) void k_tier_interleave(const uint64_t* __restr
     const uint64_t col = (uint64_t)ids.id[s] * stride + p;
     *reinterpret_cast<ulonglong2*>(out + (p * T + s) * 2) = make_ulonglong2(cnt[col], bytes[col]);
   }
+}
+
+// TierBreakdown(pos) -> ComputeMonthlyCost (pricing.go:159-240) for one (query, manifest slot) per
+// lane: k_index_tiers's read, each lane pricing its slot by the shared rule (s3imph_pricing.h).
+// The records of the workgroup's qb queries are summed in LDS (u64 sums wrap, so the order is
+// free; per_tier[id] has one writer) and then written as one contiguous run of 17 qb words.
+// Tl = max(T, 1) lanes per query: without tier data only `found` is set.
+constexpr int kCostWords = (int)(sizeof(s3imph_cost) / 8);
+static_assert(sizeof(s3imph_cost) == 136 && sizeof(s3imph_price_table) == 120, "section 5h layouts");
+__global__ __launch_bounds__(kQT) void k_index_cost(const uint64_t* __restrict__ tier, uint64_t n, uint32_t T,
+                                                    uint32_t Tl, uint32_t qb, TierSlots ids, s3imph_price_table pt,
+                                                    const uint64_t* __restrict__ qpos, uint64_t nq,
+                                                    uint64_t* __restrict__ out) {
+  extern __shared__ unsigned long long s_rec[];  // qb records
+  const uint64_t q0 = (uint64_t)blockIdx.x * qb;
+  const uint32_t nact = (uint32_t)(nq - q0 < qb ? nq - q0 : qb);
+  for (uint32_t w = threadIdx.x; w < nact * kCostWords; w += kQT) s_rec[w] = 0;
+  __syncthreads();
+  const uint32_t ql = threadIdx.x / Tl, s = threadIdx.x - ql * Tl;
+  if (ql < nact) {
+    const uint64_t p = qpos[q0 + ql];
+    if (p < n) {
+      unsigned long long* r = s_rec + ql * kCostWords;
+      unsigned long long flags = s == 0 ? 1ull << 32 : 0;  // found
+      if (s < T) {
+        const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(tier + (p * T + s) * 2);
+        const uint32_t id = ids.id[s];
+        const SlotCost c = price_slot(id, v.x, v.y, pt);
+        if (c.priced) {
+          r[4 + id] = c.tier_total;
+          if (c.tier_total + c.monitoring) atomicAdd(&r[0], c.tier_total + c.monitoring);
+          if (c.monitoring) atomicAdd(&r[1], c.monitoring);
+          if (c.min_size) atomicAdd(&r[2], c.min_size);
+          if (c.overhead) atomicAdd(&r[3], c.overhead);
+          if (v.x | v.y) flags |= 1ull << id;  // tier_mask
+        }
+      }
+      if (flags) atomicOr(&r[4 + S3IMPH_NUM_TIERS], flags);
+    }
+  }
+  __syncthreads();
+  for (uint32_t w = threadIdx.x; w < nact * kCostWords; w += kQT) out[q0 * kCostWords + w] = s_rec[w];
+}
+
+// The ranking key of every planned position, one lane each: object_count, total_bytes, or
+// s3imph_cost.total by the same rule, the lane walking its position's T slots.
+__global__ __launch_bounds__(kQT) void k_rank_keys(IndexArrays a, const uint64_t* __restrict__ tier, uint32_t T,
+                                                   TierSlots ids, s3imph_price_table pt, int key,
+                                                   const uint64_t* __restrict__ pos, uint64_t total,
+                                                   uint64_t* __restrict__ keys) {
+  const uint64_t i = (uint64_t)blockIdx.x * kQT + threadIdx.x;
+  if (i >= total) return;
+  const uint64_t p = pos[i];
+  uint64_t v = 0;
+  if (p < a.n) {
+    if (key == S3IMPH_RANK_OBJECT_COUNT) {
+      v = a.ocnt[p];
+    } else if (key == S3IMPH_RANK_TOTAL_BYTES) {
+      v = a.tbytes[p];
+    } else {
+      for (uint32_t s = 0; s < T; ++s) {
+        const ulonglong2 cb = *reinterpret_cast<const ulonglong2*>(tier + (p * T + s) * 2);
+        const SlotCost c = price_slot(ids.id[s], cb.x, cb.y, pt);
+        v += c.tier_total + c.monitoring;
+      }
+    }
+  }
+  keys[i] = v;
+}
+
+// Entry j of row r out of the sorted rows: the first min(k, len) pairs, then the padding.
+// rp == nullptr: every row is empty.
+__global__ __launch_bounds__(kQT) void k_rows_take(const uint64_t* __restrict__ rp, const uint64_t* __restrict__ spos,
+                                                   const uint64_t* __restrict__ skey, uint64_t n_rows, uint32_t k,
+                                                   uint64_t* __restrict__ top_pos, uint64_t* __restrict__ top_key,
+                                                   uint32_t* __restrict__ top_n) {
+  const uint64_t i = (uint64_t)blockIdx.x * kQT + threadIdx.x;
+  if (i >= n_rows * k) return;
+  const uint64_t r = i / k;
+  const uint32_t j = (uint32_t)(i - r * k);
+  const uint64_t lo = rp ? rp[r] : 0, len = rp ? rp[r + 1] - lo : 0;
+  const uint32_t tn = len < k ? (uint32_t)len : k;
+  top_pos[i] = j < tn ? spos[lo + j] : ~0ull;
+  top_key[i] = j < tn ? skey[lo + j] : 0;
+  if (j == 0) top_n[r] = tn;
 }
 
 // One lane per result row: the row's slice start in depth_positions and its unfiltered
@@ -657,6 +747,13 @@ struct s3imph_index {
   bool have_plan = false;
   uint64_t plan_rows = 0, plan_total_u = 0, plan_total = 0, plan_mc = 0, plan_mb = 0;
   bool plan_filtered = false;
+  // workspace of descendants_top: the filled positions, their keys and both sorted (4 x cap
+  // words), the filtered row_ptr (rows + 1), the segmented sort's temporary
+  uint64_t* top_buf = nullptr;
+  uint64_t top_cap = 0;
+  uint64_t* top_rp = nullptr;
+  uint64_t top_rp_cap = 0;
+  PrimTmp top_tmp;
 };
 
 namespace s3imph {
@@ -668,8 +765,10 @@ void index_free(s3imph_index* x) {
   if (x->ctx) (void)s3imph_ctx_destroy(x->ctx);  // drains its stream first
   for (void* p : x->owned)
     if (p) (void)hipFree(p);
-  for (uint64_t** p : {&x->row_lo, &x->row_len, &x->U, &x->sums, &x->csum, &x->cbase, &x->csums2, &x->tier_table})
+  for (uint64_t** p : {&x->row_lo, &x->row_len, &x->U, &x->sums, &x->csum, &x->cbase, &x->csums2, &x->tier_table,
+                       &x->top_buf, &x->top_rp})
     dfree(*p);
+  x->top_tmp.release();
   delete x;
 }
 
@@ -804,6 +903,63 @@ int plan_locked(s3imph_index* x, const uint64_t* d_qpos, const int32_t* d_rel, u
   x->plan_filtered = filtered;
   x->plan_mc = min_count;
   x->plan_mb = min_bytes;
+  return S3IMPH_OK;
+}
+
+// The positions of the plan's rows into out (plan_total entries, > 0); the caller holds the lock.
+int fill_locked(s3imph_index* x, uint64_t* out, const char* what, hipStream_t s) {
+  const uint64_t tu = x->plan_total_u, chunks = (tu + kChunk - 1) / kChunk;
+  if (chunks > 0x7fffffffull) {
+    x->last_msg = std::string(what) + ": more than 2^42 positions in one batch";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (x->plan_filtered)
+    k_desc_filter<kFill><<<(unsigned)chunks, kChunkT, 0, s>>>(x->a, x->U, x->row_lo, x->plan_rows, tu, x->plan_mc,
+                                                             x->plan_mb, nullptr, x->cbase, nullptr, out);
+  else
+    k_desc_fill<<<(unsigned)chunks, kChunkT, 0, s>>>(x->U, x->row_lo, x->plan_rows, tu, x->a.dpos, out);
+  HIPCHECK(hipGetLastError());
+  return S3IMPH_OK;
+}
+
+int top_locked(s3imph_index* x, int key, const s3imph_price_table& pt, uint32_t k, uint64_t* d_top_pos,
+               uint64_t* d_top_key, uint32_t* d_top_n, hipStream_t s) {
+  const uint64_t rows = x->plan_rows, total = x->plan_total;
+  if (rows == 0) return S3IMPH_OK;
+  const uint64_t* rp = nullptr;
+  uint64_t *spos = nullptr, *skey = nullptr;
+  if (total) {
+    grow(x->top_buf, x->top_cap, 4 * total);
+    uint64_t *pos = x->top_buf, *keys = pos + total;
+    spos = keys + total;
+    skey = spos + total;
+    const int rc = fill_locked(x, pos, "descendants top", s);
+    if (rc != S3IMPH_OK) return rc;
+    if (x->plan_filtered) {  // the plan wrote the filtered row_ptr to the caller only: read it off again
+      grow(x->top_rp, x->top_rp_cap, rows + 1);
+      const uint64_t tu = x->plan_total_u;
+      k_desc_filter<kRows><<<(unsigned)(tu / kChunk + 1), kChunkT, 0, s>>>(
+          x->a, x->U, x->row_lo, rows, tu, x->plan_mc, x->plan_mb, nullptr, x->cbase, x->top_rp, nullptr);
+      rp = x->top_rp;
+    } else {
+      rp = x->U;
+    }
+    TierSlots slots{};
+    std::memcpy(slots.id, x->tier_ids, sizeof slots.id);
+    k_rank_keys<<<(unsigned)((total + kQT - 1) / kQT), kQT, 0, s>>>(x->a, x->tier_table, x->T, slots, pt, key, pos, total,
+                                                                   keys);
+    HIPCHECK(hipGetLastError());
+    // the segmented sort gives a segment to one workgroup (1M positions in one row: 41 ms): a lone
+    // row is sorted device-wide instead
+    if (rows == 1)
+      sort_pairs_desc(x->top_tmp, keys, skey, pos, spos, total, s);
+    else
+      sort_rows_pairs_desc(x->top_tmp, keys, skey, pos, spos, total, rows, rp, s);
+  }
+  k_rows_take<<<(unsigned)((rows * k + kQT - 1) / kQT), kQT, 0, s>>>(rp, spos, skey, rows, k, d_top_pos, d_top_key,
+                                                                    d_top_n);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(s));
   return S3IMPH_OK;
 }
 
@@ -1064,19 +1220,95 @@ int s3imph_index_descendants_fill(s3imph_index* x, uint64_t* d_out, uint64_t cap
   try {
     HIPCHECK(hipSetDevice(x->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
-    const uint64_t tu = x->plan_total_u, chunks = (tu + kChunk - 1) / kChunk;
-    if (chunks > 0x7fffffffull) {
-      x->last_msg = "descendants fill: more than 2^42 positions in one batch";
+    const int rc = fill_locked(x, d_out, "descendants fill", s);
+    if (rc != S3IMPH_OK) return rc;
+    HIPCHECK(hipStreamSynchronize(s));
+    return S3IMPH_OK;
+  } catch (const Fail& f) {
+    x->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+int s3imph_index_cost_device(s3imph_index* x, const uint64_t* d_qpos, uint64_t nq, const s3imph_price_table* pt,
+                             s3imph_cost* d_out, void* stream) {
+  if (!x || !pt || (nq && (!d_qpos || !d_out))) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(x->mu);
+  x->last_msg.clear();
+  if (*price_table_fault(*pt)) {
+    x->last_msg = std::string("pricing: ") + price_table_fault(*pt);
+    return S3IMPH_ERR_INVALID;
+  }
+  if (nq == 0) return S3IMPH_OK;
+  try {
+    HIPCHECK(hipSetDevice(x->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+    const uint32_t Tl = x->T ? x->T : 1, qb = kQT / Tl;
+    const uint64_t blocks = (nq + qb - 1) / qb;
+    if (blocks > 0x7fffffffull) {
+      x->last_msg = "pricing: more than 2^31 workgroups of queries in one batch";
       return S3IMPH_ERR_INVALID;
     }
-    if (x->plan_filtered)
-      k_desc_filter<kFill><<<(unsigned)chunks, kChunkT, 0, s>>>(x->a, x->U, x->row_lo, x->plan_rows, tu, x->plan_mc,
-                                                               x->plan_mb, nullptr, x->cbase, nullptr, d_out);
-    else
-      k_desc_fill<<<(unsigned)chunks, kChunkT, 0, s>>>(x->U, x->row_lo, x->plan_rows, tu, x->a.dpos, d_out);
+    TierSlots slots{};
+    std::memcpy(slots.id, x->tier_ids, sizeof slots.id);
+    k_index_cost<<<(unsigned)blocks, kQT, qb * sizeof(s3imph_cost), s>>>(x->tier_table, x->a.n, x->T, Tl, qb, slots, *pt, d_qpos, nq,
+                                                  reinterpret_cast<uint64_t*>(d_out));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     return S3IMPH_OK;
+  } catch (const Fail& f) {
+    x->last_msg = f.msg;
+    return f.code;
+  }
+}
+
+int s3imph_index_descendants_top(s3imph_index* x, int key, const s3imph_price_table* pt, uint32_t k,
+                                 uint64_t* d_top_pos, uint64_t* d_top_key, uint32_t* d_top_n, void* stream) {
+  if (!x) return S3IMPH_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(x->mu);
+  x->last_msg.clear();
+  const bool cost = key == S3IMPH_RANK_MONTHLY_COST;
+  if (k == 0 || (key != S3IMPH_RANK_OBJECT_COUNT && key != S3IMPH_RANK_TOTAL_BYTES && !cost) || (cost && !pt)) {
+    x->last_msg = "descendants top: invalid argument";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (cost && *price_table_fault(*pt)) {
+    x->last_msg = std::string("pricing: ") + price_table_fault(*pt);
+    return S3IMPH_ERR_INVALID;
+  }
+  if (!x->have_plan) {
+    x->last_msg = "descendants top: no plan";
+    return S3IMPH_ERR_STATE;
+  }
+  if (!cost && !x->a.ocnt) {
+    x->last_msg = "descendants top: the index has no object_count / total_bytes to rank by";
+    return S3IMPH_ERR_STATE;
+  }
+  if (cost && x->T == 0) {
+    x->last_msg = "descendants top: the index has no tier data to price";
+    return S3IMPH_ERR_STATE;
+  }
+  if (x->plan_rows * k >= (1ull << 31)) {
+    x->last_msg = "descendants top: n_rows * k is 2^31 or more";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (x->plan_total >= (1ull << 32)) {
+    x->last_msg = "descendants top: 2^32 positions or more in the plan";
+    return S3IMPH_ERR_INVALID;
+  }
+  if (x->plan_rows && (!d_top_pos || !d_top_key || !d_top_n)) {
+    x->last_msg = "descendants top: invalid argument";
+    return S3IMPH_ERR_INVALID;
+  }
+  try {
+    HIPCHECK(hipSetDevice(x->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+    const s3imph_price_table none{};
+    std::string msg;
+    const int rc = retry_on_nomem(x->ctx, s, &msg,
+                                  [&] { return top_locked(x, key, cost ? *pt : none, k, d_top_pos, d_top_key, d_top_n, s); });
+    if (rc != S3IMPH_OK && x->last_msg.empty()) x->last_msg = msg;
+    return rc;
   } catch (const Fail& f) {
     x->last_msg = f.msg;
     return f.code;

@@ -19,7 +19,9 @@ byte-sorted listing; ``sort_objects`` and ``build_index_from_unsorted_objects`` 
 order (the stable byte-order sort and the gather run on the GPU too); ``parse_inventory_csv`` and
 ``build_index_from_inventory_csv`` start from the inventory's CSV text.  With one tier id
 per object (``TIERS``, ``tier_from_s3``) both also carry the per-storage-class statistics that
-``Index.tier_breakdown*`` answer from.
+``Index.tier_breakdown*`` answer from, and ``PriceTable`` / ``Index.monthly_cost*`` price them
+(pricing.ComputeMonthlyCost per position, on the GPU); ``Index.descendants_top`` keeps the k
+largest positions of every descendants row by cost, bytes or object count.
 
 Every compute call goes through the HIP library; there is no CPU fallback.
 If libs3imph.so is missing, importing this module raises.
@@ -88,6 +90,8 @@ EXPORTS = (
     "s3imph_index_from_unsorted_objects_host",
     "s3imph_csv_header_schema", "s3imph_csv_plan_device", "s3imph_csv_fill_device", "s3imph_csv_parse_host",
     "s3imph_index_from_csv_host", "s3imph_csv_geometry",
+    "s3imph_price_table_default", "s3imph_price_table_load", "s3imph_price_table_save",
+    "s3imph_compute_monthly_cost", "s3imph_index_cost_device", "s3imph_index_descendants_top",
 )
 NUM_TIERS = 12  # S3IMPH_NUM_TIERS
 
@@ -181,6 +185,21 @@ class CsvInfo(ctypes.Structure):
     def as_dict(self) -> dict:
         return {f: getattr(self, f) for f, _ in self._fields_}
 
+
+class _PriceTable(ctypes.Structure):
+    """s3imph_price_table (include/s3imph.h, section 5h)."""
+    _fields_ = [("per_gb_month", ctypes.c_double * 12), ("priced_mask", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+                ("monitoring_per_1000_objects", ctypes.c_double), ("standard_price_per_gb", ctypes.c_double)]
+
+
+# s3imph_cost: what Index.cost_device returns, one record per queried position
+COST_DTYPE = np.dtype([("total", "<u8"), ("monitoring", "<u8"), ("min_object_size", "<u8"),
+                       ("glacier_overhead", "<u8"), ("per_tier", "<u8", (12,)), ("tier_mask", "<u4"), ("found", "<u4")])
+RANK_OBJECT_COUNT = 0
+RANK_TOTAL_BYTES = 1
+RANK_MONTHLY_COST = 2
+_RANK_KEYS = {"count": RANK_OBJECT_COUNT, "object_count": RANK_OBJECT_COUNT, "bytes": RANK_TOTAL_BYTES,
+              "total_bytes": RANK_TOTAL_BYTES, "cost": RANK_MONTHLY_COST}
 
 # s3imph_node: what Index.nodes returns, one record per queried position
 NODE_DTYPE = np.dtype([("pos", "<u8"), ("subtree_end", "<u8"), ("object_count", "<u8"), ("total_bytes", "<u8"),
@@ -280,6 +299,12 @@ def _load():
         "s3imph_index_from_csv_host": (i32, [i32, P(vp), P(u64), u64, P(CsvSchema), i32, ctypes.c_uint32, cp,
                                              P(CsvInfo), cp, sz]),
         "s3imph_csv_geometry": (None, [P(ctypes.c_uint32), P(ctypes.c_uint32)]),
+        "s3imph_price_table_default": (i32, [P(_PriceTable)]),
+        "s3imph_price_table_load": (i32, [cp, P(_PriceTable), cp, sz]),
+        "s3imph_price_table_save": (i32, [cp, P(_PriceTable), cp, sz]),
+        "s3imph_compute_monthly_cost": (i32, [vp, vp, vp, u64, P(_PriceTable), vp]),
+        "s3imph_index_cost_device": (i32, [vp, vp, u64, P(_PriceTable), vp, vp]),
+        "s3imph_index_descendants_top": (i32, [vp, i32, P(_PriceTable), ctypes.c_uint32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -364,6 +389,145 @@ def keys_to_blob(keys) -> tuple[np.ndarray, np.ndarray]:
         offs[1:] = np.cumsum([len(k) for k in bs], dtype=np.uint64)
     blob = np.frombuffer(b"".join(bs), np.uint8).copy() if bs else np.zeros(0, np.uint8)
     return blob, offs
+
+
+# ------------------------------------------------------------------------- pricing --
+class PriceTable:
+    """pricing.PriceTable (pkg/pricing/pricing.go:25-35) keyed by tier id underneath:
+    ``per_gb_month`` is a dict by tier name holding the priced tiers, the two scalars are
+    ``monitoring_per_1000_objects`` and ``standard_price_per_gb``."""
+
+    def __init__(self, per_gb_month: dict | None = None, monitoring_per_1000_objects: float = 0.0,
+                 standard_price_per_gb: float = 0.0):
+        self.per_gb_month = dict(per_gb_month or {})
+        self.monitoring_per_1000_objects = float(monitoring_per_1000_objects)
+        self.standard_price_per_gb = float(standard_price_per_gb)
+
+    @classmethod
+    def _from_c(cls, c: "_PriceTable") -> "PriceTable":
+        return cls({TIERS[t][1]: c.per_gb_month[t] for t in range(NUM_TIERS) if (c.priced_mask >> t) & 1},
+                   c.monitoring_per_1000_objects, c.standard_price_per_gb)
+
+    def _c(self) -> "_PriceTable":
+        """The C struct; a name that is none of the twelve tiers is left out, as the loader does."""
+        c = _PriceTable()
+        ids = {name: t for t, name, _ in TIERS}
+        for name, price in self.per_gb_month.items():
+            if name in ids:
+                c.per_gb_month[ids[name]] = float(price)
+                c.priced_mask |= 1 << ids[name]
+        c.monitoring_per_1000_objects = self.monitoring_per_1000_objects
+        c.standard_price_per_gb = self.standard_price_per_gb
+        return c
+
+    @classmethod
+    def default_us_east_1(cls) -> "PriceTable":
+        """DefaultUSEast1Prices (pricing.go:67-93)."""
+        c = _PriceTable()
+        _check(LIB.s3imph_price_table_default(ctypes.byref(c)))
+        return cls._from_c(c)
+
+    @classmethod
+    def load(cls, path: str) -> "PriceTable":
+        """LoadPriceTable (pricing.go:96-108)."""
+        c = _PriceTable()
+        err = ctypes.create_string_buffer(1024)
+        _check(LIB.s3imph_price_table_load(os.fsencode(path), ctypes.byref(c), err, 1024), err)
+        return cls._from_c(c)
+
+    def save(self, path: str) -> None:
+        """SavePriceTable (pricing.go:111-122)."""
+        err = ctypes.create_string_buffer(1024)
+        _check(LIB.s3imph_price_table_save(os.fsencode(path), ctypes.byref(self._c()), err, 1024), err)
+
+    def __eq__(self, other):
+        return isinstance(other, PriceTable) and (self.per_gb_month, self.monitoring_per_1000_objects,
+                                                  self.standard_price_per_gb) == (
+            other.per_gb_month, other.monitoring_per_1000_objects, other.standard_price_per_gb)
+
+    def __repr__(self):
+        return (f"PriceTable({self.per_gb_month!r}, {self.monitoring_per_1000_objects!r}, "
+                f"{self.standard_price_per_gb!r})")
+
+
+def _pt_c(pt) -> "_PriceTable":
+    if pt is None:
+        pt = PriceTable.default_us_east_1()
+    return pt if isinstance(pt, _PriceTable) else pt._c()
+
+
+def _cost_dict(r) -> dict:
+    """One COST_DTYPE record as a dict shaped like pricing.CostResult (per-tier by name, only the
+    tier_mask tiers) plus ``found``."""
+    return {"found": bool(r["found"]), "total": int(r["total"]), "monitoring": int(r["monitoring"]),
+            "min_object_size": int(r["min_object_size"]), "glacier_overhead": int(r["glacier_overhead"]),
+            "per_tier": {TIERS[t][1]: int(r["per_tier"][t]) for t in range(NUM_TIERS) if (int(r["tier_mask"]) >> t) & 1}}
+
+
+def compute_monthly_cost_record(breakdown, pt=None) -> np.ndarray:
+    """s3imph_compute_monthly_cost over a breakdown [(tier id, name, bytes, count)] (what
+    Index.tier_breakdown[_all] returns per position): one COST_DTYPE record, host only."""
+    ids = np.array([e[0] for e in breakdown], np.uint8)
+    tb = np.array([e[2] for e in breakdown], np.uint64)
+    tc = np.array([e[3] for e in breakdown], np.uint64)
+    out = np.zeros(1, COST_DTYPE)
+    rc = LIB.s3imph_compute_monthly_cost(_np_ptr(ids), _np_ptr(tc), _np_ptr(tb), len(ids), ctypes.byref(_pt_c(pt)),
+                                         ctypes.c_void_p(out.ctypes.data))
+    _check(rc, None, "pricing")
+    return out[0]
+
+
+def compute_monthly_cost(breakdown, pt=None) -> dict:
+    """pricing.ComputeMonthlyCost (pricing.go:159-240) as a dict; see compute_monthly_cost_record."""
+    return _cost_dict(compute_monthly_cost_record(breakdown, pt))
+
+
+_MIN_SIZE_TIERS = frozenset((1, 2, 3))
+_MONITORING_TIERS = frozenset((7, 8, 9, 10, 11))
+_GLACIER_TIERS = frozenset((4, 5, 10, 11))
+
+
+def compute_detailed_breakdown(breakdown, pt=None) -> list:
+    """pricing.ComputeDetailedBreakdown (pricing.go:256-312): one dict of dollars per priced tier
+    of the breakdown.  A display helper, in Python floats."""
+    pt = PriceTable.default_us_east_1() if pt is None else pt
+    ids = {name: t for t, name, _ in TIERS}
+    out = []
+    for tier, name, nbytes, count in breakdown:
+        if name not in pt.per_gb_month or name not in ids:
+            continue
+        price = float(pt.per_gb_month[name])
+        avg = nbytes // count if count else 0
+        cb = {"tier_name": name, "object_count": count, "bytes": nbytes, "avg_object_size_bytes": avg,
+              "storage_cost": nbytes / 1073741824.0 * price, "min_size_penalty": 0.0, "monitoring_cost": 0.0,
+              "glacier_overhead": 0.0}
+        if tier in _MIN_SIZE_TIERS and 0 < avg < 131072:
+            cb["min_size_penalty"] = (((131072 - avg) * count) & ((1 << 64) - 1)) / 1073741824.0 * price
+        if tier in _MONITORING_TIERS and pt.monitoring_per_1000_objects > 0:
+            mon = count if avg >= 131072 else (count // 2 if avg > 0 else 0)
+            cb["monitoring_cost"] = mon / 1000.0 * pt.monitoring_per_1000_objects
+        if tier in _GLACIER_TIERS and count > 0:
+            cb["glacier_overhead"] = ((count * 32768) & ((1 << 64) - 1)) / 1073741824.0 * price
+            cb["glacier_overhead"] += ((count * 8192) & ((1 << 64) - 1)) / 1073741824.0 * pt.standard_price_per_gb
+        cb["total_cost"] = cb["storage_cost"] + cb["min_size_penalty"] + cb["monitoring_cost"] + cb["glacier_overhead"]
+        out.append(cb)
+    return out
+
+
+def format_cost_dollars(dollars: float) -> str:
+    """pricing.FormatCostDollars (pricing.go:320-331)."""
+    if dollars < 0.01:
+        return "$%.6f" % dollars
+    if dollars < 1:
+        return "$%.4f" % dollars
+    if dollars < 100:
+        return "$%.2f" % dollars
+    return "$%.0f" % dollars
+
+
+def format_cost(microdollars: int) -> str:
+    """pricing.FormatCost (pricing.go:315-317)."""
+    return format_cost_dollars(float(microdollars) / 1_000_000)
 
 
 # ------------------------------------------------------------------- builder mirror --
@@ -1197,6 +1361,57 @@ class Index:
         """TierBreakdownForPrefix (index.go:394) per key: tier_breakdown at the key's position,
         [] for a key the index does not hold."""
         return self.tier_breakdown(self.lookup_device(*self._keys_dev(*keys_to_blob(keys))))
+
+    # -- monthly cost (section 5h) ------------------------------------------------------
+    def cost_device(self, pos, pt=None, stream=None):
+        """s3imph_index_cost_device: an (nq, 17) int64 tensor holding one s3imph_cost per row
+        (COST_DTYPE on the host).  pt None: the default us-east-1 table."""
+        import torch
+        d_pos = self._pos_dev(pos)
+        nq = int(d_pos.shape[0])
+        out = torch.empty((max(nq, 1), COST_DTYPE.itemsize // 8), dtype=torch.int64, device=self.dev)
+        self._fail(LIB.s3imph_index_cost_device(self._h, _dev_ptr(d_pos), nq, ctypes.byref(_pt_c(pt)), _dev_ptr(out),
+                                                _stream_ptr(stream)), "monthly cost")
+        return out[:nq]
+
+    def cost_records(self, pos, pt=None) -> np.ndarray:
+        """One COST_DTYPE record per position."""
+        t = self.cost_device(pos, pt)
+        if t.shape[0] == 0:
+            return np.zeros(0, COST_DTYPE)
+        return t.cpu().numpy().reshape(-1).view(COST_DTYPE)
+
+    def monthly_cost(self, pos, pt=None) -> list:
+        """query --estimate-cost per position: TierBreakdown(pos) -> ComputeMonthlyCost as dicts
+        shaped like CostResult (per-tier by name, only the tier_mask tiers), plus ``found``."""
+        return [_cost_dict(r) for r in self.cost_records(pos, pt)]
+
+    def monthly_cost_for_prefix(self, keys, pt=None) -> list:
+        """monthly_cost at each key's position; found False for a key the index does not hold."""
+        return self.monthly_cost(self.lookup_device(*self._keys_dev(*keys_to_blob(keys))), pt)
+
+    def descendants_top(self, pos, rel=None, max_rel: int = 0, key="cost", k: int = 10, pt=None, min_count: int = 0,
+                        min_bytes: int = 0, stream=None):
+        """descendants_plan followed by s3imph_index_descendants_top: (top_n int32 (n_rows,),
+        top_pos int64 (n_rows, k), top_key int64 (n_rows, k)) on the device, u64 bits; key is
+        "cost", "bytes" or "count" (or a RANK_* value)."""
+        _, _, n_rows, _ = self.descendants_plan(pos, rel, max_rel, min_count, min_bytes, stream=stream)
+        return self.top_of_plan(n_rows, key, k, pt, stream)
+
+    def top_of_plan(self, n_rows: int, key="cost", k: int = 10, pt=None, stream=None):
+        """s3imph_index_descendants_top on the rows of the last descendants_plan."""
+        import torch
+        kid = _RANK_KEYS.get(key, key) if isinstance(key, str) else int(key)
+        if isinstance(kid, str):
+            raise ValueError(f"unknown ranking key {key!r}")
+        cells = max(n_rows * max(k, 0), 1) if n_rows * max(k, 0) < (1 << 31) else 1
+        top_pos = torch.empty(cells, dtype=torch.int64, device=self.dev)
+        top_key = torch.empty(cells, dtype=torch.int64, device=self.dev)
+        top_n = torch.empty(max(n_rows, 1), dtype=torch.int32, device=self.dev)
+        c_pt = ctypes.byref(_pt_c(pt)) if kid == RANK_MONTHLY_COST else None
+        self._fail(LIB.s3imph_index_descendants_top(self._h, kid, c_pt, k, _dev_ptr(top_pos), _dev_ptr(top_key),
+                                                    _dev_ptr(top_n), _stream_ptr(stream)), "descendants top")
+        return (top_n[:n_rows], top_pos[: n_rows * k].reshape(n_rows, k), top_key[: n_rows * k].reshape(n_rows, k))
 
     def last_error(self) -> str:
         return LIB.s3imph_index_last_error(self._h).decode(errors="replace")
