@@ -905,6 +905,144 @@ int s3imph_index_descendants_top(s3imph_index *idx, int key, const s3imph_price_
                                  uint32_t *d_top_n /* n_rows */, void *stream);
 
 /* ------------------------------------------------------------------------
+ * 5i. Sorted runs of prefix rows merged on the GPU, and an index built in chunks: the back of
+ *     pkg/extsort's pipeline.  Pipeline.flushAggregator (pipeline.go:703-783) drains the
+ *     aggregator into a sorted RUN of PrefixRows whenever memory fills; runMergeBuildPhase
+ *     (pipeline.go:786-914) k-way merges the runs (MergeIterator.Next, merger.go:104-140, which
+ *     sums equal prefixes with PrefixRow.Merge, types.go:82-91; the rounds are
+ *     ParallelMerger.MergeAll, parallel_merge.go:122-190) and feeds IndexBuilder.  Here a listing
+ *     that does not fit one GPU is cut into chunks, each chunk is parsed / sorted / aggregated on
+ *     the GPU by sections 5d-5g into a run kept in HOST memory, and the runs — far fewer rows than
+ *     objects — are merged in HBM at the end.
+ *
+ *     Input of the device merge: ONE row set in HBM sorted in K stretches — d_blob / d_offsets
+ *     (N + 1 entries) under section 5d's contract (any byte alignment, offsets[0] need not be 0,
+ *     readable to round_up(offsets[N], 8)), d_depth, d_count, d_bytes (N entries each), optionally
+ *     the 12 + 12 tier columns, column-major (column t at t * tier_stride, tier_stride >= N; both
+ *     NULL: no tier columns are read or produced; one without the other is S3IMPH_ERR_INVALID),
+ *     and a HOST array run_starts[K + 1] with run_starts[0] = 0, non-decreasing, run_starts[K] = N:
+ *     run r is rows run_starts[r] .. run_starts[r + 1]; empty runs are allowed.
+ *
+ *     What MergeIterator yields: the rows in byte order (Go's string <: a proper prefix first, 0x00
+ *     and bytes >= 0x80 ordinary), one row per distinct prefix; Count, TotalBytes and every tier
+ *     column summed mod 2^64 over ALL input rows with that prefix, equal neighbours inside one run
+ *     included (the loop at merger.go:125-137 folds them too).  Depth is taken from the member in
+ *     the lowest run, in a tie the lowest row index: the reference keeps whichever row its heap pops
+ *     first, which is unspecified among equals; this is the library's deterministic choice.
+ *     present_mask has bit t set iff some MERGED row has tier_count[t] | tier_bytes[t] != 0
+ *     (indexbuild.go:192-196).
+ *
+ *     Refusals, all S3IMPH_ERR_INVALID with a message worded "merge: ..." (s3imph_ctx_last_error):
+ *     a run that is not non-decreasing (first_unsorted = the global row index; the reference does
+ *     not check — a tightening; a descent exactly at a run boundary is no error), run_starts
+ *     malformed, K > S3IMPH_MERGE_MAX_RUNS, N >= 2^32 (this and every null or shape check come
+ *     before any device work), more than 2^30 output rows.  N == 0 (any K, 0 included) is OK with
+ *     zero rows.
+ *
+ *     Memory: the scratch lives in ctx, grows on demand and is released by
+ *     s3imph_release_workspaces: 32 bytes per input row (the merged order 4, head flags and head
+ *     lengths with their scans 8 + 8, the heads' places 4, the heads' sources 8) plus 4 K / S bytes
+ *     per row for the splitter table (S = the sample step of s3imph_merge_geometry) and the scans'
+ *     temporary.  The merge is out of place: input and output rows coexist in HBM.
+ * ------------------------------------------------------------------------ */
+#define S3IMPH_MERGE_MAX_RUNS 64
+typedef struct s3imph_merge_info {
+    uint64_t n_in;            /* N */
+    uint64_t n_out;           /* distinct prefixes: the rows the fill writes */
+    uint64_t blob_bytes;      /* bytes of the output prefixes */
+    uint64_t first_unsorted;  /* smallest global i with row[i] < row[i-1] inside one run; UINT64_MAX when none */
+    uint64_t present_mask;    /* of the merged rows; 0 without tier columns */
+    uint32_t max_depth_seen;  /* deepest output depth */
+    uint32_t n_runs;          /* K */
+} s3imph_merge_info;          /* 48 bytes */
+
+/* MergeIterator over K runs in HBM (merger.go:104-140), first half: the order, the fold and the
+ * scans that size the result; fills *info and keeps the plan in ctx (a later plan replaces it).
+ * The input arrays must stay valid and unchanged until the fill.  Synchronous on `stream`. */
+int s3imph_merge_rows_plan_device(s3imph_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_offsets,
+                                  const uint32_t *d_depth, const uint64_t *d_count, const uint64_t *d_bytes,
+                                  const uint64_t *d_tier_count, const uint64_t *d_tier_bytes, uint64_t tier_stride,
+                                  const uint64_t *run_starts, uint32_t k, s3imph_merge_info *info, void *stream);
+
+/* The merged rows of the last plan (PrefixRow.Merge, types.go:82-91), under
+ * s3imph_aggregate_fill_device's contract: d_blob (blob_cap >= round_up(blob_bytes, 8); the padding
+ * is written as zeros, so the result goes straight into s3imph_build_device), d_offsets (n_out + 1
+ * entries, starting at 0), n_cap >= n_out entries each of d_depth, d_count, d_bytes, and — required
+ * iff the plan had tier inputs — the tier columns, column t at t * n_cap.  S3IMPH_ERR_STATE without
+ * a plan, S3IMPH_ERR_INVALID when a capacity is short.  Synchronous on `stream`. */
+int s3imph_merge_rows_fill_device(s3imph_ctx *ctx, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offsets,
+                                  uint32_t *d_depth, uint64_t *d_count, uint64_t *d_bytes,
+                                  uint64_t *d_tier_count, uint64_t *d_tier_bytes, uint64_t n_cap, void *stream);
+
+/* The merge's geometry, for tests that place run lengths on its edges: every *sample_step-th row of
+ * a run is a splitter. */
+void s3imph_merge_geometry(uint32_t *sample_step);
+
+/* One sorted run in host memory: n rows in the blob / offsets layout (offsets[0] need not be 0),
+ * their depths, counts and bytes, and the tier columns (column t at t * tier_stride, tier_stride
+ * >= n) — both NULL or both set.  n == 0 may leave every pointer NULL. */
+typedef struct s3imph_row_run {
+    const uint8_t *blob;
+    const uint64_t *offsets;
+    const uint32_t *depth;
+    const uint64_t *count, *bytes, *tier_count, *tier_bytes;
+    uint64_t n, tier_stride;
+} s3imph_row_run;
+
+/* The merge from host memory (merger.go:104-140; parallel_merge.go:122-190): the runs are
+ * concatenated on upload, their offsets rebased, merged, and the rows brought back.  The outputs
+ * are allocated by the library as in s3imph_aggregate_tiers_host (release each with s3imph_free);
+ * the tier outputs are S3IMPH_NUM_TIERS x *n u64 each, column t at t * *n, and come back NULL when
+ * the runs carry no tier columns (tier_count / tier_bytes / present_mask may then be NULL
+ * themselves).  Runs that mix "with tiers" and "without" are S3IMPH_ERR_INVALID, before any device
+ * work (an empty run counts with neither).  k > S3IMPH_MERGE_MAX_RUNS merges in rounds of at most
+ * 64 CONTIGUOUS runs, as MergeAll does: contiguous groups keep "the lowest run wins" and the sums
+ * are associative, so the result does not depend on the grouping.  *info (nullable) describes the
+ * whole merge: n_in over all runs, first_unsorted as a row index into their concatenation.  No row
+ * at all: *n = 0, *offsets = [0], the others NULL, no device touched. */
+int s3imph_merge_rows_host(int device, const s3imph_row_run *runs, uint64_t k, uint8_t **blob, uint64_t **offsets,
+                           uint32_t **depth, uint64_t **object_count, uint64_t **total_bytes,
+                           uint64_t **tier_count, uint64_t **tier_bytes, uint64_t *present_mask, uint64_t *n,
+                           s3imph_merge_info *info, char *err, size_t errlen);
+
+/* runMergeBuildPhase (pipeline.go:786-914): the runs merged, then the back half of
+ * s3imph_index_from_objects[_tiers]_host in the same device residency — MPHF build, finalize with
+ * the merged depths, the twelve index files, the tier files when the runs carry tier columns,
+ * manifest.json.  k == 0 or only empty runs writes the empty index s3imph_index_open accepts
+ * (pipeline.go:796-806).  A missing out_dir is S3IMPH_ERR_IO before the device is selected; the
+ * out-of-memory retry of the host builds applies; error texts are "merge: ...", then the existing
+ * "build MPHF: ...". */
+int s3imph_index_from_rows_host(int device, const s3imph_row_run *runs, uint64_t k, const char *out_dir,
+                                char *err, size_t errlen);
+
+/* The chunked build — Pipeline's ingest loop (pipeline.go:370-517, :703-783): a handle that holds
+ * runs in host memory.  Each add_objects (a listing chunk in ANY order; tiers: one id per object,
+ * required iff the set was made with_tiers, ignored otherwise) and each add_csv (CSV buffers as
+ * in s3imph_index_from_csv_host) is one parse / sort / aggregate on the GPU with the handle's
+ * max_depth, followed by a D2H of the rows into the handle: one run; a chunk without an object
+ * adds none.  add_rows copies a caller's sorted run (its tier columns must match with_tiers).
+ * build is s3imph_index_from_rows_host over the held runs and may be repeated.
+ *
+ * The contract: the directory equals, file for file, the one
+ * s3imph_index_from_unsorted_objects_host (with tiers when with_tiers) writes for the concatenation
+ * of the chunks — manifest.json's created_at excepted.  Only one chunk's listing is in HBM at a
+ * time; the merge needs the runs' rows there twice (in and out).  Spilling runs to disk, run files
+ * (runfile.go's EXTS format) and compressed runs are out of scope.  Calls on one handle are
+ * serialized by the handle. */
+typedef struct s3imph_rowset s3imph_rowset;
+int s3imph_rowset_new(int device, uint32_t max_depth, int with_tiers, s3imph_rowset **out, char *err, size_t errlen);
+int s3imph_rowset_add_objects(s3imph_rowset *rs, const uint8_t *keys, const uint64_t *key_offsets,
+                              const uint64_t *sizes, const uint8_t *tiers, uint64_t m, char *err, size_t errlen);
+int s3imph_rowset_add_csv(s3imph_rowset *rs, const uint8_t *const *csv, const uint64_t *csv_len, uint64_t n_files,
+                          const s3imph_csv_schema *schema, char *err, size_t errlen);
+int s3imph_rowset_add_rows(s3imph_rowset *rs, const s3imph_row_run *run, char *err, size_t errlen);
+/* Runs held, and rows held over all runs. */
+uint64_t s3imph_rowset_runs(const s3imph_rowset *rs);
+uint64_t s3imph_rowset_rows(const s3imph_rowset *rs);
+int s3imph_rowset_build(s3imph_rowset *rs, const char *out_dir, char *err, size_t errlen);
+int s3imph_rowset_close(s3imph_rowset *rs);
+
+/* ------------------------------------------------------------------------
  * 6. Deterministic synthetic prefix sets (bench/test support, not on the path).
  *    kind: 0 = s3-like, lengths uniform in [max(10, avg/2), 3avg/2],
  *              distinct and byte-sorted;

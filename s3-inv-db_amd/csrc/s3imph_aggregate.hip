@@ -680,18 +680,6 @@ void upload_keys(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t
 
 namespace {
 
-// The prefix rows of a host listing, left in HBM (owned by g).
-struct DevRows {
-  uint64_t n = 0, blob_bytes = 0;
-  uint8_t* blob = nullptr;
-  uint64_t *offsets = nullptr, *ocnt = nullptr, *tbytes = nullptr;
-  uint32_t* depth = nullptr;
-  // with tiers: kNT columns of n entries each, the present tiers
-  uint64_t *tier_count = nullptr, *tier_bytes = nullptr;
-  uint64_t present_mask = 0;
-  uint64_t m = 0;  // objects of the listing the rows were made from
-};
-
 // The listing's device copy put into byte order (s3imph_sort.hip): sort, gather out of place,
 // free the unsorted copy.  A listing found sorted stays as it is.
 int sort_listing(s3imph_ctx* c, DevGuard& g, uint8_t*& d_keys, uint64_t*& d_koff, uint64_t*& d_sizes,
@@ -726,14 +714,16 @@ int sort_listing(s3imph_ctx* c, DevGuard& g, uint8_t*& d_keys, uint64_t*& d_koff
   }
 }
 
+}  // namespace
+
 // H2D of the listing, plan, fill (with `tiers`: the tier forms and the tier columns too; with
 // `unsorted`: the sort and the gather first); the listing's device copy is freed before returning.
 // With `csv` the listing comes from CSV buffers parsed on the device (s3imph_csv.hip), always in
 // file order, so sorted here; `tiers` then only says whether tiers are wanted.  No object at all:
 // out->m == 0 and no rows.
 int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes,
-                   uint64_t m, uint32_t max_depth, DevRows* out, std::string* msg, const uint8_t* tiers = nullptr,
-                   bool unsorted = false, const CsvFiles* csv = nullptr) {
+                   uint64_t m, uint32_t max_depth, DevRows* out, std::string* msg, const uint8_t* tiers, bool unsorted,
+                   const CsvFiles* csv) {
   hipStream_t s = c->own_stream;
   uint8_t *d_keys = nullptr, *d_tiers = nullptr;
   uint64_t *d_koff = nullptr, *d_sizes = nullptr;
@@ -791,6 +781,8 @@ int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64
   g.drop(d_tiers);
   return rc;
 }
+
+namespace {
 
 template <typename T>
 T* host_array(uint64_t count) {
@@ -1004,6 +996,93 @@ int s3imph_aggregate_tiers_host(int device, const uint8_t* keys, const uint64_t*
 
 }  // extern "C"
 
+// Rows in HBM -> every array of the index directory on the host: the MPHF build over the rows'
+// blob, the finalize with their depths, the D2H.  The rows stay in HBM throughout.
+int s3imph::index_arrays_from_rows(s3imph_ctx* c, DevGuard& g, DevRows& r, bool tiers, IndexHostArrays& h,
+                                   hipStream_t s, std::string* pmsg) {
+  std::string& msg = *pmsg;
+  const uint64_t n = h.n = r.n;
+  int rc2;
+  if (tiers) {  // the columns of the present tiers leave HBM before the build needs the room
+    h.present_mask = r.present_mask;
+    h.tcount.resize(kNT * n);
+    h.tcbytes.resize(kNT * n);
+    for (int t = 0; t < kNT; ++t) {
+      if (!((h.present_mask >> t) & 1)) continue;
+      staged_copy(c, false, h.tcount.data() + t * n, r.tier_count + t * n, n * 8);
+      staged_copy(c, false, h.tcbytes.data() + t * n, r.tier_bytes + t * n, n * 8);
+    }
+    g.drop(r.tier_count);
+    g.drop(r.tier_bytes);
+  }
+  uint64_t *d_fp = nullptr, *d_pos = nullptr, *d_send = nullptr, *d_dpos = nullptr, *d_doff = nullptr;
+  uint32_t *d_depth = nullptr, *d_maxds = nullptr;
+  g.make(d_fp, n);
+  g.make(d_pos, n);
+  s3imph_build_info binfo;
+  rc2 = build_single(c, r.blob, r.offsets, nullptr, n, d_fp, d_pos, s, &binfo, &msg);
+  if (rc2 != S3IMPH_OK) return rc2;
+  HIPCHECK(hipStreamSynchronize(s));
+  g.make(d_send, n);
+  g.make(d_dpos, n);
+  g.make(d_depth, n);
+  g.make(d_maxds, n);
+  uint64_t cap = 64;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    g.make(d_doff, cap);
+    rc2 = finalize_device(c, r.blob, r.offsets, r.depth, n, d_depth, d_send, d_maxds, d_dpos, d_doff, cap, &h.md,
+                          s, &msg);
+    if (rc2 == S3IMPH_OK) break;
+    if (rc2 != S3IMPH_ERR_INVALID || attempt) return rc2;
+    cap = (uint64_t)h.md + 2;
+    g.drop(d_doff);
+    d_doff = nullptr;
+  }
+  HIPCHECK(hipStreamSynchronize(s));
+  uint64_t mlen = 0;
+  h.mph.resize(binfo.mph_bin_len);
+  rc2 = marshal_locked(c, h.mph.data(), h.mph.size(), &mlen, &msg);
+  if (rc2 != S3IMPH_OK) return rc2;
+  h.mph.resize(mlen);
+  h.blob.resize(r.blob_bytes);
+  h.offs.resize(n + 1);
+  h.doff.resize((uint64_t)h.md + 2);
+  for (auto* v : {&h.fp, &h.pos, &h.send, &h.dpos, &h.ocnt, &h.tbytes}) v->resize(n);
+  h.depth.resize(n);
+  h.maxds.resize(n);
+  if (r.blob_bytes) HIPCHECK(hipMemcpy(h.blob.data(), r.blob, r.blob_bytes, hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(h.doff.data(), d_doff, h.doff.size() * 8, hipMemcpyDeviceToHost));
+  staged_copy(c, false, h.offs.data(), r.offsets, (n + 1) * 8);
+  staged_copy(c, false, h.fp.data(), d_fp, n * 8);
+  staged_copy(c, false, h.pos.data(), d_pos, n * 8);
+  staged_copy(c, false, h.send.data(), d_send, n * 8);
+  staged_copy(c, false, h.dpos.data(), d_dpos, n * 8);
+  staged_copy(c, false, h.ocnt.data(), r.ocnt, n * 8);
+  staged_copy(c, false, h.tbytes.data(), r.tbytes, n * 8);
+  staged_copy(c, false, h.depth.data(), d_depth, n * 4);
+  staged_copy(c, false, h.maxds.data(), d_maxds, n * 4);
+  return S3IMPH_OK;
+}
+
+// The directory's files from the host arrays (n == 0: the empty index s3imph_index_open accepts).
+int s3imph::write_index_dir(const std::string& dir, IndexHostArrays& h, bool tiers, std::string* msg) {
+  const uint64_t n = h.n;
+  if (n == 0) {
+    h.offs = {0};
+    h.doff = {0, 0};  // writeEmpty-like: maxDepth 0 -> offsets [0, 0]
+  }
+  int rc = write_index_files(dir, h.mph.data(), h.mph.size(), h.fp.data(), h.pos.data(), n, h.blob.data(),
+                             h.offs.data(), msg);
+  if (rc == S3IMPH_OK)
+    rc = write_finalize_files(dir, h.depth.data(), h.send.data(), h.maxds.data(), h.doff.data(), h.doff.size(),
+                              h.dpos.data(), n, msg);
+  if (rc == S3IMPH_OK) rc = write_stats_files(dir, h.ocnt.data(), h.tbytes.data(), n, msg);
+  if (rc == S3IMPH_OK && tiers)
+    rc = write_tier_files(dir, h.present_mask, h.tcount.data(), h.tcbytes.data(), n, n, msg);
+  if (rc == S3IMPH_OK) rc = write_manifest(dir, n, h.md, msg);
+  return rc;
+}
+
 // s3imph_index_from_objects_host, with `tiers` s3imph_index_from_objects_tiers_host, and with
 // `unsorted` s3imph_index_from_unsorted_objects_host (s3imph_sort.hip).
 int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
@@ -1022,12 +1101,7 @@ int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* 
   }
   std::string msg;
   try {
-    uint64_t n = 0;
-    uint32_t md = 0;
-    std::vector<uint8_t> mph, blob;
-    std::vector<uint64_t> fp, pos, offs, send, dpos, doff, ocnt, tbytes, tcount, tcbytes;
-    uint64_t present_mask = 0;
-    std::vector<uint32_t> depth, maxds;
+    IndexHostArrays h;
     uint64_t csv_bytes = 0;
     for (uint64_t i = 0; csv && i < csv->n_files; ++i) csv_bytes += csv->len[i];
     if (m || csv_bytes) {
@@ -1045,84 +1119,16 @@ int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* 
         DevRows r;
         int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers, unsorted, csv);
         if (rc2 != S3IMPH_OK) return rc2;
-        n = r.n;
+        h.n = r.n;
         if (r.m == 0) return S3IMPH_OK;  // CSV text without an object: the empty index below
-        if (tiers) {  // the columns of the present tiers leave HBM before the build needs the room
-          present_mask = r.present_mask;
-          tcount.resize(kNT * n);
-          tcbytes.resize(kNT * n);
-          for (int t = 0; t < kNT; ++t) {
-            if (!((present_mask >> t) & 1)) continue;
-            staged_copy(c, false, tcount.data() + t * n, r.tier_count + t * n, n * 8);
-            staged_copy(c, false, tcbytes.data() + t * n, r.tier_bytes + t * n, n * 8);
-          }
-          g.drop(r.tier_count);
-          g.drop(r.tier_bytes);
-        }
-        uint64_t *d_fp = nullptr, *d_pos = nullptr, *d_send = nullptr, *d_dpos = nullptr, *d_doff = nullptr;
-        uint32_t *d_depth = nullptr, *d_maxds = nullptr;
-        g.make(d_fp, n);
-        g.make(d_pos, n);
-        s3imph_build_info binfo;
-        rc2 = build_single(c, r.blob, r.offsets, nullptr, n, d_fp, d_pos, s, &binfo, &msg);
-        if (rc2 != S3IMPH_OK) return rc2;
-        HIPCHECK(hipStreamSynchronize(s));
-        g.make(d_send, n);
-        g.make(d_dpos, n);
-        g.make(d_depth, n);
-        g.make(d_maxds, n);
-        uint64_t cap = 64;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-          g.make(d_doff, cap);
-          rc2 = finalize_device(c, r.blob, r.offsets, r.depth, n, d_depth, d_send, d_maxds, d_dpos, d_doff, cap, &md,
-                                s, &msg);
-          if (rc2 == S3IMPH_OK) break;
-          if (rc2 != S3IMPH_ERR_INVALID || attempt) return rc2;
-          cap = (uint64_t)md + 2;
-          g.drop(d_doff);
-          d_doff = nullptr;
-        }
-        HIPCHECK(hipStreamSynchronize(s));
-        uint64_t mlen = 0;
-        mph.resize(binfo.mph_bin_len);
-        rc2 = marshal_locked(c, mph.data(), mph.size(), &mlen, &msg);
-        if (rc2 != S3IMPH_OK) return rc2;
-        mph.resize(mlen);
-        blob.resize(r.blob_bytes);
-        offs.resize(n + 1);
-        doff.resize((uint64_t)md + 2);
-        for (auto* v : {&fp, &pos, &send, &dpos, &ocnt, &tbytes}) v->resize(n);
-        depth.resize(n);
-        maxds.resize(n);
-        if (r.blob_bytes) HIPCHECK(hipMemcpy(blob.data(), r.blob, r.blob_bytes, hipMemcpyDeviceToHost));
-        HIPCHECK(hipMemcpy(doff.data(), d_doff, doff.size() * 8, hipMemcpyDeviceToHost));
-        staged_copy(c, false, offs.data(), r.offsets, (n + 1) * 8);
-        staged_copy(c, false, fp.data(), d_fp, n * 8);
-        staged_copy(c, false, pos.data(), d_pos, n * 8);
-        staged_copy(c, false, send.data(), d_send, n * 8);
-        staged_copy(c, false, dpos.data(), d_dpos, n * 8);
-        staged_copy(c, false, ocnt.data(), r.ocnt, n * 8);
-        staged_copy(c, false, tbytes.data(), r.tbytes, n * 8);
-        staged_copy(c, false, depth.data(), d_depth, n * 4);
-        staged_copy(c, false, maxds.data(), d_maxds, n * 4);
-        return S3IMPH_OK;
+        return index_arrays_from_rows(c, g, r, tiers != nullptr, h, s, &msg);
       });
       if (rc != S3IMPH_OK) {
         set_err(err, errlen, msg);
         return rc;
       }
     }
-    if (n == 0) {
-      offs = {0};
-      doff = {0, 0};  // writeEmpty-like: maxDepth 0 -> offsets [0, 0]
-    }
-    int rc = write_index_files(dir, mph.data(), mph.size(), fp.data(), pos.data(), n, blob.data(), offs.data(), &msg);
-    if (rc == S3IMPH_OK)
-      rc = write_finalize_files(dir, depth.data(), send.data(), maxds.data(), doff.data(), doff.size(), dpos.data(), n,
-                                &msg);
-    if (rc == S3IMPH_OK) rc = write_stats_files(dir, ocnt.data(), tbytes.data(), n, &msg);
-    if (rc == S3IMPH_OK && tiers) rc = write_tier_files(dir, present_mask, tcount.data(), tcbytes.data(), n, n, &msg);
-    if (rc == S3IMPH_OK) rc = write_manifest(dir, n, md, &msg);
+    const int rc = write_index_dir(dir, h, tiers != nullptr, &msg);
     if (rc != S3IMPH_OK) set_err(err, errlen, msg);
     return rc;
   } catch (const Fail& f) {

@@ -2341,6 +2341,7 @@ bool reclaim_cached(s3imph_ctx* keep, const void* keep_set) {
       agg_scratch_free(c);
       sort_scratch_free(c);
       csv_scratch_free(c);
+      merge_scratch_free(c);
       c->have_build = false;
       c->rank_valid = false;
       any = true;
@@ -2351,6 +2352,7 @@ bool reclaim_cached(s3imph_ctx* keep, const void* keep_set) {
     agg_scratch_free(keep);
     sort_scratch_free(keep);
     csv_scratch_free(keep);
+    merge_scratch_free(keep);
     any = true;
   }
   if (keep) (void)hipSetDevice(keep->device);
@@ -2932,6 +2934,7 @@ int s3imph_ctx_destroy(s3imph_ctx* c) {
   agg_scratch_free(c);
   sort_scratch_free(c);
   csv_scratch_free(c);
+  merge_scratch_free(c);
   if (c->d.xo) (void)hipStreamSynchronize(c->d.xo);
   delete c->d.xcomm;
   c->d.xcomm = nullptr;
@@ -3341,6 +3344,7 @@ int s3imph_release_workspaces(void) {
     agg_scratch_free(c);
     sort_scratch_free(c);
     csv_scratch_free(c);
+    merge_scratch_free(c);
     c->have_build = false;
     c->rank_valid = false;
   }

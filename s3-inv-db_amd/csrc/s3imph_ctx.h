@@ -236,6 +236,7 @@ struct FinScratch;  // s3imph_finalize.hip
 struct AggScratch;  // s3imph_aggregate.hip
 struct SortScratch;  // s3imph_sort.hip
 struct CsvScratch;  // s3imph_csv.hip
+struct MergeScratch;  // s3imph_merge.hip
 }
 
 struct s3imph_ctx {
@@ -244,6 +245,7 @@ struct s3imph_ctx {
   s3imph::AggScratch* agg = nullptr;  // aggregation scratch and the last plan (s3imph_aggregate.hip), lazily made
   s3imph::SortScratch* srt = nullptr;  // listing sort / gather scratch (s3imph_sort.hip), lazily made
   s3imph::CsvScratch* csv = nullptr;  // CSV parse scratch and the last plan (s3imph_csv.hip), lazily made
+  s3imph::MergeScratch* mrg = nullptr;  // row merge scratch and the last plan (s3imph_merge.hip), lazily made
   uint32_t* mid = nullptr;            // k_mid_levels scratch (kMidScratchU32), lazily made
   Rec* split = nullptr;               // k_tile_split scratch, made for sets big enough for 2^15+ tiles
   hipStream_t own_stream = nullptr;
@@ -443,6 +445,41 @@ struct CsvFiles {
 };
 int csv_listing(s3imph_ctx* c, DevGuard& g, const CsvFiles& f, uint8_t*& d_keys, uint64_t*& d_koff,
                 uint64_t*& d_sizes, uint8_t*& d_tiers, uint64_t* m, hipStream_t s, std::string* msg);
+// The prefix rows of a listing or of a merge, left in HBM (owned by a DevGuard).
+struct DevRows {
+  uint64_t n = 0, blob_bytes = 0;
+  uint8_t* blob = nullptr;
+  uint64_t *offsets = nullptr, *ocnt = nullptr, *tbytes = nullptr;
+  uint32_t* depth = nullptr;
+  // with tiers: S3IMPH_NUM_TIERS columns of n entries each, the present tiers
+  uint64_t *tier_count = nullptr, *tier_bytes = nullptr;
+  uint64_t present_mask = 0;
+  uint64_t m = 0;  // objects of the listing the rows were made from
+};
+// H2D of a host listing, plan, fill (s3imph_aggregate.hip); with `tiers` the tier columns too,
+// with `unsorted` the sort and the gather first, with `csv` the listing parsed from CSV buffers
+// (`tiers` then only says whether tiers are wanted).  The listing's device copy is freed before
+// returning; no object at all: out->m == 0 and no rows.
+int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64_t* koff, const uint64_t* sizes,
+                   uint64_t m, uint32_t max_depth, DevRows* out, std::string* msg, const uint8_t* tiers = nullptr,
+                   bool unsorted = false, const CsvFiles* csv = nullptr);
+// The back half every "rows in HBM, index directory out" path shares (s3imph_aggregate.hip):
+// index_arrays_from_rows builds the MPHF over r's blob, finalizes with r's depths and brings every
+// array of the directory to the host (the tier columns first, freed before the build needs the
+// room); write_index_dir writes the files and the manifest (n == 0: the empty index).
+struct IndexHostArrays {
+  uint64_t n = 0, present_mask = 0;
+  uint32_t md = 0;
+  std::vector<uint8_t> mph, blob;
+  std::vector<uint64_t> fp, pos, offs, send, dpos, doff, ocnt, tbytes, tcount, tcbytes;
+  std::vector<uint32_t> depth, maxds;
+};
+int index_arrays_from_rows(s3imph_ctx* c, DevGuard& g, DevRows& r, bool tiers, IndexHostArrays& h, hipStream_t s,
+                           std::string* msg);
+int write_index_dir(const std::string& dir, IndexHostArrays& h, bool tiers, std::string* msg);
+// Row merge (s3imph_merge.hip): plan and fill over one row set in HBM sorted in k stretches; both
+// wait for the stream.
+void merge_scratch_free(s3imph_ctx* c);
 // A context (s3imph_ctx_create) whose multi-GPU collectives go through `comm` (owned).
 s3imph_ctx* make_dist_ctx(int device, Comm* comm, int rank, int nranks, std::string* msg);
 

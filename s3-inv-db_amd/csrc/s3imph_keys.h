@@ -32,6 +32,24 @@ __device__ __forceinline__ uint64_t slash_bits(uint64_t x, uint64_t valid) {
   return z;
 }
 
+// Three-way byte order of two keys of one blob (Go's string <: unsigned bytes, a proper prefix
+// first): negative, zero or positive as key a (blob address a0, alen bytes) sorts before, equals
+// or sorts after key b.  Word by word, the comparison k_sort_check and k_agg_keys make inline.
+__device__ __forceinline__ int compare_keys(const uint8_t* blob, uint64_t a0, uint64_t alen, uint64_t b0,
+                                            uint64_t blen, uint64_t end8) {
+  const uint64_t mm = min(alen, blen);  // bytes both keys have
+  for (uint64_t k = 0; k < mm; k += 8) {
+    const uint64_t wa = load8(blob, a0 + k, end8), wb = load8(blob, b0 + k, end8);
+    const uint64_t x = wa ^ wb;
+    if (x) {
+      const unsigned fd = (unsigned)(__builtin_ctzll(x) >> 3);
+      if (fd < mm - k) return ((wa >> (8 * fd)) & 0xff) < ((wb >> (8 * fd)) & 0xff) ? -1 : 1;
+      break;  // they differ only past the shorter key's end, in this last word
+    }
+  }
+  return alen < blen ? -1 : (alen > blen ? 1 : 0);
+}
+
 // First index in [lo, hi) with U[index] > u, or hi.
 __device__ __forceinline__ uint64_t first_above(const uint64_t* __restrict__ U, uint64_t lo, uint64_t hi,
                                                 uint64_t u) {

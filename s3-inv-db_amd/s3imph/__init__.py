@@ -92,7 +92,12 @@ EXPORTS = (
     "s3imph_index_from_csv_host", "s3imph_csv_geometry",
     "s3imph_price_table_default", "s3imph_price_table_load", "s3imph_price_table_save",
     "s3imph_compute_monthly_cost", "s3imph_index_cost_device", "s3imph_index_descendants_top",
+    "s3imph_merge_rows_plan_device", "s3imph_merge_rows_fill_device", "s3imph_merge_geometry",
+    "s3imph_merge_rows_host", "s3imph_index_from_rows_host",
+    "s3imph_rowset_new", "s3imph_rowset_add_objects", "s3imph_rowset_add_csv", "s3imph_rowset_add_rows",
+    "s3imph_rowset_runs", "s3imph_rowset_rows", "s3imph_rowset_build", "s3imph_rowset_close",
 )
+MERGE_MAX_RUNS = 64  # S3IMPH_MERGE_MAX_RUNS
 NUM_TIERS = 12  # S3IMPH_NUM_TIERS
 
 
@@ -184,6 +189,27 @@ class CsvInfo(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class MergeInfo(ctypes.Structure):
+    """s3imph_merge_info: what a row merge plan found (include/s3imph.h, section 5i)."""
+    _fields_ = [
+        ("n_in", ctypes.c_uint64), ("n_out", ctypes.c_uint64), ("blob_bytes", ctypes.c_uint64),
+        ("first_unsorted", ctypes.c_uint64), ("present_mask", ctypes.c_uint64),
+        ("max_depth_seen", ctypes.c_uint32), ("n_runs", ctypes.c_uint32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class RowRun(ctypes.Structure):
+    """s3imph_row_run: one sorted run of prefix rows in host memory (include/s3imph.h, section 5i)."""
+    _fields_ = [
+        ("blob", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("depth", ctypes.c_void_p),
+        ("count", ctypes.c_void_p), ("bytes", ctypes.c_void_p), ("tier_count", ctypes.c_void_p),
+        ("tier_bytes", ctypes.c_void_p), ("n", ctypes.c_uint64), ("tier_stride", ctypes.c_uint64),
+    ]
 
 
 class _PriceTable(ctypes.Structure):
@@ -305,6 +331,21 @@ def _load():
         "s3imph_compute_monthly_cost": (i32, [vp, vp, vp, u64, P(_PriceTable), vp]),
         "s3imph_index_cost_device": (i32, [vp, vp, u64, P(_PriceTable), vp, vp]),
         "s3imph_index_descendants_top": (i32, [vp, i32, P(_PriceTable), ctypes.c_uint32, vp, vp, vp, vp]),
+        "s3imph_merge_rows_plan_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, u64, vp, ctypes.c_uint32,
+                                                P(MergeInfo), vp]),
+        "s3imph_merge_rows_fill_device": (i32, [vp, vp, u64, vp, vp, vp, vp, vp, vp, u64, vp]),
+        "s3imph_merge_geometry": (None, [P(ctypes.c_uint32)]),
+        "s3imph_merge_rows_host": (i32, [i32, P(RowRun), u64, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp), P(vp),
+                                         P(u64), P(u64), P(MergeInfo), cp, sz]),
+        "s3imph_index_from_rows_host": (i32, [i32, P(RowRun), u64, cp, cp, sz]),
+        "s3imph_rowset_new": (i32, [i32, ctypes.c_uint32, i32, P(vp), cp, sz]),
+        "s3imph_rowset_add_objects": (i32, [vp, vp, vp, vp, vp, u64, cp, sz]),
+        "s3imph_rowset_add_csv": (i32, [vp, P(vp), P(u64), u64, P(CsvSchema), cp, sz]),
+        "s3imph_rowset_add_rows": (i32, [vp, P(RowRun), cp, sz]),
+        "s3imph_rowset_runs": (u64, [vp]),
+        "s3imph_rowset_rows": (u64, [vp]),
+        "s3imph_rowset_build": (i32, [vp, cp, cp, sz]),
+        "s3imph_rowset_close": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -923,6 +964,57 @@ class DeviceBuilder:
         return {"keys": keys[: (end + 7) // 8 * 8] if d_keys is None else keys, "offsets": offs[: n + 1],
                 "sizes": sizes[:n], "tiers": None if tiers is None else tiers[:n], "key_bytes": info["key_bytes"]}
 
+    def merge_rows_plan(self, d_blob, d_offsets, d_depth, d_count, d_bytes, run_starts, d_tier_count=None,
+                        d_tier_bytes=None, tier_stride: int = 0, stream=None) -> dict:
+        """s3imph_merge_rows_plan_device: MergeIterator (merger.go:104-140) over one row set in HBM
+        sorted in K stretches; run_starts is a HOST sequence of K + 1 row indices.  Returns
+        s3imph_merge_info as a dict (n_in, n_out, blob_bytes, first_unsorted, present_mask,
+        max_depth_seen, n_runs); a refusal raises MPHFError with that dict as ``.info``.  The input
+        tensors must stay valid and unchanged until merge_rows_fill."""
+        rs = np.ascontiguousarray(run_starts, np.uint64)
+        info = MergeInfo()
+        rc = LIB.s3imph_merge_rows_plan_device(self._h, _dev_ptr(d_blob), _dev_ptr(d_offsets), _dev_ptr(d_depth),
+                                               _dev_ptr(d_count), _dev_ptr(d_bytes), _dev_ptr(d_tier_count),
+                                               _dev_ptr(d_tier_bytes), tier_stride,
+                                               ctypes.c_void_p(rs.ctypes.data) if rs.size else None,
+                                               max(len(rs) - 1, 0), ctypes.byref(info), _stream_ptr(stream))
+        self.last_merge = info.as_dict()
+        self.last_merge["tiered"] = d_tier_count is not None
+        if rc != OK:
+            e = MPHFError(rc, self.last_error() or f"merge: {status_string(rc)}")
+            e.info = self.last_merge
+            raise e
+        return self.last_merge
+
+    def merge_rows_fill(self, n_cap: int | None = None, blob_cap: int | None = None, device=None, stream=None) -> dict:
+        """s3imph_merge_rows_fill_device: the merged rows of the last plan as torch tensors: blob
+        (uint8, padded with zeros to 8 bytes), offsets (int64, n + 1), depth (int32), object_count /
+        total_bytes (int64 holding the u64 bits), and after a plan with tier columns tier_count /
+        tier_bytes as (NUM_TIERS, n_cap) int64 tensors (else None), n, blob_bytes, present_mask."""
+        import torch
+        info = getattr(self, "last_merge", None) or {"n_out": 0, "blob_bytes": 0, "tiered": False, "present_mask": 0}
+        n, nbytes = info["n_out"], info["blob_bytes"]
+        n_cap = n if n_cap is None else n_cap
+        blob_cap = (nbytes + 7) // 8 * 8 if blob_cap is None else blob_cap
+        dev = f"cuda:{self.device}" if device is None else device
+        blob = torch.empty(max(blob_cap, 8), dtype=torch.uint8, device=dev)
+        offs = torch.empty(max(n_cap, n) + 1, dtype=torch.int64, device=dev)
+        depth = torch.empty(max(n_cap, 1), dtype=torch.int32, device=dev)
+        ocnt = torch.empty(max(n_cap, 1), dtype=torch.int64, device=dev)
+        tbytes = torch.empty(max(n_cap, 1), dtype=torch.int64, device=dev)
+        tc = tb = None
+        if info.get("tiered"):
+            tc = torch.empty((NUM_TIERS, max(n_cap, 1)), dtype=torch.int64, device=dev)
+            tb = torch.empty((NUM_TIERS, max(n_cap, 1)), dtype=torch.int64, device=dev)
+        rc = LIB.s3imph_merge_rows_fill_device(self._h, _dev_ptr(blob), blob_cap, _dev_ptr(offs), _dev_ptr(depth),
+                                               _dev_ptr(ocnt), _dev_ptr(tbytes), _dev_ptr(tc), _dev_ptr(tb), n_cap,
+                                               _stream_ptr(stream))
+        if rc != OK:
+            raise MPHFError(rc, self.last_error() or f"merge: {status_string(rc)}")
+        return {"blob": blob[: (nbytes + 7) // 8 * 8], "offsets": offs[: n + 1], "depth": depth[:n],
+                "object_count": ocnt[:n], "total_bytes": tbytes[:n], "tier_count": tc, "tier_bytes": tb, "n": n,
+                "blob_bytes": nbytes, "present_mask": info.get("present_mask", 0)}
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             LIB.s3imph_ctx_destroy(self._h)
@@ -1122,6 +1214,161 @@ def build_index_from_inventory_csv(files, schema, out_dir: str, with_tiers: bool
     _check(LIB.s3imph_index_from_csv_host(device, ptrs, lens, k, ctypes.byref(_csv_schema(schema)), int(with_tiers),
                                           max_depth, os.fsencode(out_dir), ctypes.byref(info), err, 1024), err)
     return info.as_dict()
+
+
+def merge_geometry() -> int:
+    """The row merge's sample step (s3imph_merge_geometry): every step-th row of a run is a
+    splitter; for tests that place run lengths on its edges."""
+    step = ctypes.c_uint32()
+    LIB.s3imph_merge_geometry(ctypes.byref(step))
+    return int(step.value)
+
+
+def _row_runs(runs):
+    """Runs as (blob, offsets, depth, count, bytes[, tier_count, tier_bytes[, mask]]) tuples — the
+    tuples aggregate() returns — -> (RowRun array, k, the arrays kept alive)."""
+    keep, out = [], []
+    for run in runs:
+        run = tuple(run)
+        if len(run) not in (5, 7, 8):
+            raise ValueError("a run is (blob, offsets, depth, count, bytes[, tier_count, tier_bytes])")
+        blob = np.ascontiguousarray(run[0], np.uint8)
+        offs = np.ascontiguousarray(run[1], np.uint64)
+        n = len(offs) - 1
+        depth = np.ascontiguousarray(run[2], np.uint32)
+        cnt = np.ascontiguousarray(run[3], np.uint64)
+        tot = np.ascontiguousarray(run[4], np.uint64)
+        if n < 0 or len(depth) != n or len(cnt) != n or len(tot) != n:
+            raise ValueError("a run's depth, count and bytes must hold one entry per row")
+        tc = tb = None
+        if len(run) >= 7 and run[5] is not None:
+            tc = np.ascontiguousarray(run[5], np.uint64).reshape(NUM_TIERS, -1)
+            tb = np.ascontiguousarray(run[6], np.uint64).reshape(NUM_TIERS, -1)
+            if tc.shape != (NUM_TIERS, n) or tb.shape != (NUM_TIERS, n):
+                raise ValueError("a run's tier columns must be (NUM_TIERS, n)")
+        keep.append((blob, offs, depth, cnt, tot, tc, tb))
+        p = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        out.append(RowRun(p(blob), offs.ctypes.data if n else None, p(depth), p(cnt), p(tot),
+                          tc.ctypes.data if tc is not None and n else None,
+                          tb.ctypes.data if tb is not None and n else None, n, n))
+    k = len(out)
+    return (RowRun * max(k, 1))(*out), k, keep
+
+
+def merge_rows(runs, device: int = 0, with_info: bool = False):
+    """MergeIterator + PrefixRow.Merge (merger.go:104-140, types.go:82-91) on the GPU
+    (s3imph_merge_rows_host): sorted runs of prefix rows — tuples (blob, offsets, depth, count,
+    bytes[, tier_count, tier_bytes]) as aggregate() returns them — merged into one: the same
+    tuple, with present_mask appended when the runs carry tier columns.  Equal prefixes are summed;
+    the depth comes from the lowest run.  More than MERGE_MAX_RUNS runs merge in rounds.  With
+    ``with_info`` the s3imph_merge_info dict is appended."""
+    arr, k, keep = _row_runs(runs)
+    out = [ctypes.c_void_p() for _ in range(7)]
+    n, mask, info = ctypes.c_uint64(), ctypes.c_uint64(), MergeInfo()
+    err = ctypes.create_string_buffer(1024)
+    rc = LIB.s3imph_merge_rows_host(device, arr, k, *[ctypes.byref(p) for p in out], ctypes.byref(mask),
+                                    ctypes.byref(n), ctypes.byref(info), err, 1024)
+    try:
+        if rc != OK:
+            e = MPHFError(rc, err.value.decode(errors="replace") or status_string(rc))
+            e.info = info.as_dict()
+            raise e
+        nn = n.value
+
+        def take(p, dtype, count):
+            a = np.zeros(count, dtype)
+            if count and p.value:
+                ctypes.memmove(a.ctypes.data, p.value, a.nbytes)
+            return a
+
+        offsets = take(out[1], np.uint64, nn + 1)
+        rows = (take(out[0], np.uint8, int(offsets[-1])), offsets, take(out[2], np.uint32, nn),
+                take(out[3], np.uint64, nn), take(out[4], np.uint64, nn))
+        if any(x[5] is not None and len(x[1]) > 1 for x in keep):
+            rows += (take(out[5], np.uint64, NUM_TIERS * nn).reshape(NUM_TIERS, nn),
+                     take(out[6], np.uint64, NUM_TIERS * nn).reshape(NUM_TIERS, nn), int(mask.value))
+        return rows + (info.as_dict(),) if with_info else rows
+    finally:
+        for p in out:
+            if p.value:
+                LIB.s3imph_free(p)
+
+
+def build_index_from_rows(runs, out_dir: str, device: int = 0) -> None:
+    """runMergeBuildPhase (pipeline.go:786-914; s3imph_index_from_rows_host): sorted runs of prefix
+    rows in, index directory out — merge, MPHF build and finalize in one device residency; the
+    tier files are written when the runs carry tier columns.  No rows: the empty index."""
+    arr, k, keep = _row_runs(runs)
+    err = ctypes.create_string_buffer(1024)
+    _check(LIB.s3imph_index_from_rows_host(device, arr, k, os.fsencode(out_dir), err, 1024), err)
+    del keep
+
+
+class RowSet:
+    """The chunked build (s3imph_rowset_*; Pipeline's ingest loop, pipeline.go:370-517, :703-783):
+    chunks of a listing that does not fit one GPU are each sorted and aggregated on the GPU into a
+    run held in host memory; build() merges the runs on the GPU and writes the directory
+    build_index_from_unsorted_objects writes for the concatenation of the chunks."""
+
+    def __init__(self, max_depth: int = 0, with_tiers: bool = False, device: int = 0):
+        self._h = ctypes.c_void_p()
+        self.with_tiers = bool(with_tiers)
+        err = ctypes.create_string_buffer(1024)
+        _check(LIB.s3imph_rowset_new(device, max_depth, int(self.with_tiers), ctypes.byref(self._h), err, 1024), err)
+
+    def add_objects(self, keys_blob, key_offsets, sizes, tiers=None) -> None:
+        """One chunk of the listing, in any order: one run (none for a chunk without an object)."""
+        blob, offs, sz, m = _listing(keys_blob, key_offsets, sizes)
+        tr = None if tiers is None else _tier_ids(tiers, m)
+        err = ctypes.create_string_buffer(1024)
+        _check(LIB.s3imph_rowset_add_objects(self._h, _np_ptr(blob), _np_ptr(offs), _np_ptr(sz), _np_ptr(tr), m,
+                                             err, 1024), err)
+
+    def add_csv(self, files, schema) -> None:
+        """Decompressed inventory CSV buffers (a list of bytes-likes), parsed on the GPU: one run."""
+        bufs = [np.frombuffer(bytes(f), np.uint8) if not isinstance(f, np.ndarray)
+                else np.ascontiguousarray(f, np.uint8) for f in files]
+        k = len(bufs)
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        lens = (ctypes.c_uint64 * max(k, 1))(*[b.size for b in bufs])
+        err = ctypes.create_string_buffer(1024)
+        _check(LIB.s3imph_rowset_add_csv(self._h, ptrs, lens, k, ctypes.byref(_csv_schema(schema)), err, 1024), err)
+
+    def add_rows(self, run) -> None:
+        """A caller's sorted run (a tuple as merge_rows takes them), copied."""
+        arr, _, keep = _row_runs([run])
+        err = ctypes.create_string_buffer(1024)
+        _check(LIB.s3imph_rowset_add_rows(self._h, arr, err, 1024), err)
+        del keep
+
+    @property
+    def runs(self) -> int:
+        return int(LIB.s3imph_rowset_runs(self._h))
+
+    @property
+    def rows(self) -> int:
+        return int(LIB.s3imph_rowset_rows(self._h))
+
+    def build(self, out_dir: str) -> None:
+        err = ctypes.create_string_buffer(1024)
+        _check(LIB.s3imph_rowset_build(self._h, os.fsencode(out_dir), err, 1024), err)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            LIB.s3imph_rowset_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def write_manifest(out_dir: str, node_count: int, max_depth: int) -> None:
