@@ -28,6 +28,7 @@ If libs3imph.so is missing, importing this module raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
@@ -909,7 +910,8 @@ class DeviceBuilder:
         without d_tiers), key_bytes.  keys_cap defaults to what the listing needs."""
         import torch
         dev = f"cuda:{self.device}" if d_key_offsets is None else d_key_offsets.device
-        nbytes = int(d_key_offsets[m] - d_key_offsets[0]) if m else 0
+        with _torch_on(stream, dev):  # the read-back waits for the stream that produces the offsets
+            nbytes = int(d_key_offsets[m] - d_key_offsets[0]) if m else 0
         keys_cap = (nbytes + 7) // 8 * 8 if keys_cap is None else keys_cap
         keys = torch.empty(max(keys_cap, 8), dtype=torch.uint8, device=dev)
         offs = torch.empty(m + 1, dtype=torch.int64, device=dev)
@@ -1577,10 +1579,11 @@ class Index:
         """s3imph_index_tiers_device: (out int64 (nq, T, 2) holding count, bytes as u64 bits; mask
         int32 (nq,)) on the device; T == 0 gives empty tensors."""
         import torch
-        d_pos = self._pos_dev(pos)
-        nq, t = int(d_pos.shape[0]), int(LIB.s3imph_index_tier_count(self._h))
-        out = torch.zeros((max(nq, 1), max(t, 1), 2), dtype=torch.int64, device=self.dev)
-        mask = torch.zeros(max(nq, 1), dtype=torch.int32, device=self.dev)
+        with _torch_on(stream, self.dev):  # the fills are ordered before the library's writes
+            d_pos = self._pos_dev(pos)
+            nq, t = int(d_pos.shape[0]), int(LIB.s3imph_index_tier_count(self._h))
+            out = torch.zeros((max(nq, 1), max(t, 1), 2), dtype=torch.int64, device=self.dev)
+            mask = torch.zeros(max(nq, 1), dtype=torch.int32, device=self.dev)
         self._fail(LIB.s3imph_index_tiers_device(self._h, _dev_ptr(d_pos), nq, _dev_ptr(out), _dev_ptr(mask),
                                                  _stream_ptr(stream)), "tier breakdown")
         return out[:nq, :t], mask[:nq]
@@ -1614,7 +1617,8 @@ class Index:
         """s3imph_index_cost_device: an (nq, 17) int64 tensor holding one s3imph_cost per row
         (COST_DTYPE on the host).  pt None: the default us-east-1 table."""
         import torch
-        d_pos = self._pos_dev(pos)
+        with _torch_on(stream, self.dev):
+            d_pos = self._pos_dev(pos)
         nq = int(d_pos.shape[0])
         out = torch.empty((max(nq, 1), COST_DTYPE.itemsize // 8), dtype=torch.int64, device=self.dev)
         self._fail(LIB.s3imph_index_cost_device(self._h, _dev_ptr(d_pos), nq, ctypes.byref(_pt_c(pt)), _dev_ptr(out),
@@ -1703,7 +1707,8 @@ class Index:
     def nodes_device(self, pos, stream=None):
         """s3imph_index_nodes_device: an (nq, 6) int64 tensor holding one s3imph_node per row."""
         import torch
-        d_pos = self._pos_dev(pos)
+        with _torch_on(stream, self.dev):
+            d_pos = self._pos_dev(pos)
         nq = int(d_pos.shape[0])
         out = torch.empty((max(nq, 1), NODE_DTYPE.itemsize // 8), dtype=torch.int64, device=self.dev)
         self._fail(LIB.s3imph_index_nodes_device(self._h, _dev_ptr(d_pos), nq, _dev_ptr(out), _stream_ptr(stream)),
@@ -1733,20 +1738,21 @@ class Index:
         DESC_AT; rel None: DESC_UPTO with max_rel.  Returns (levels int32[nq], row_ptr
         int64[n_rows + 1], n_rows, total), tensors on the device."""
         import torch
-        d_pos = self._pos_dev(pos)
-        nq = int(d_pos.shape[0])
-        if rel is not None:
-            mode, rows = DESC_AT, nq
-            if torch.is_tensor(rel):
-                d_rel = rel.to(device=self.dev, dtype=torch.int32).contiguous()
+        with _torch_on(stream, self.dev):  # conversions and the zero fill ahead of the library's work
+            d_pos = self._pos_dev(pos)
+            nq = int(d_pos.shape[0])
+            if rel is not None:
+                mode, rows = DESC_AT, nq
+                if torch.is_tensor(rel):
+                    d_rel = rel.to(device=self.dev, dtype=torch.int32).contiguous()
+                else:
+                    d_rel = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(rel, np.int32), (nq,)))
+                                             .copy()).to(self.dev)
             else:
-                d_rel = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(rel, np.int32), (nq,)))
-                                         .copy()).to(self.dev)
-        else:
-            mode, rows, d_rel = DESC_UPTO, nq * min(max(max_rel, 0), self.max_depth), None
-        cap = rows + 1 if row_ptr_cap is None else row_ptr_cap
-        levels = torch.empty(max(nq, 1), dtype=torch.int32, device=self.dev)
-        row_ptr = torch.zeros(max(cap, 1), dtype=torch.int64, device=self.dev)
+                mode, rows, d_rel = DESC_UPTO, nq * min(max(max_rel, 0), self.max_depth), None
+            cap = rows + 1 if row_ptr_cap is None else row_ptr_cap
+            levels = torch.empty(max(nq, 1), dtype=torch.int32, device=self.dev)
+            row_ptr = torch.zeros(max(cap, 1), dtype=torch.int64, device=self.dev)
         n_rows, total = ctypes.c_uint64(), ctypes.c_uint64()
         self._fail(LIB.s3imph_index_descendants_plan(self._h, _dev_ptr(d_pos), _dev_ptr(d_rel), nq, mode, max_rel,
                                                      min_count, min_bytes, _dev_ptr(levels), _dev_ptr(row_ptr), cap,
@@ -1950,6 +1956,20 @@ def _stream_ptr(stream):
     if isinstance(stream, int):
         return ctypes.c_void_p(stream)
     return ctypes.c_void_p(stream.cuda_stream)
+
+
+@contextlib.contextmanager
+def _torch_on(stream, device):
+    """The wrappers' own torch work (zero fills, conversions of host arguments, sizes read back)
+    goes to the stream the library call is given: queued on torch's current stream it would be
+    unordered with the library's work whenever ``stream=`` names another, non-blocking one."""
+    if stream is None or torch is None:
+        yield
+        return
+    if not isinstance(stream, torch.cuda.Stream):
+        stream = torch.cuda.ExternalStream(int(stream), device=device)
+    with torch.cuda.stream(stream):
+        yield
 
 
 @dataclass

@@ -404,6 +404,83 @@ def test_api_edges(s3, chunky):
     idx.close()
 
 
+# ---- the row scan past 1024 scan blocks ------------------------------------------------------
+SCAN_BLOCK = 2048                    # rows per scan block (k_rows_reduce / k_rows_down)
+SCAN_PASS = 1024 * SCAN_BLOCK        # rows one pass of k_rows_top covers: 2^21
+TINY_KEYS = [b"a/", b"a/x/", b"a/x/1/", b"a/y/", b"a/z/", b"b/", b"b/p/", b"b/q/", b"c/", b"c/r/", b"d/", b"e/"]
+
+
+@pytest.fixture(scope="module")
+def tiny(s3, oracle_lib, tmp_path_factory):
+    """Twelve nodes without a root, rows of 0 to 3 positions, depths 1 to 3; stats that a filter
+    of min_count = 1 splits (every third node has none)."""
+    n = len(TINY_KEYS)
+    stats = (np.arange(n, dtype=np.uint64) % np.uint64(3), np.full(n, 7, np.uint64))
+    t = Tree(s3, oracle_lib, tmp_path_factory.mktemp("tiny"), TINY_KEYS, stats)
+    assert t.arr["max_depth"] == 3
+    yield t
+    t.idx.close()
+
+
+def _expand(per_node, qi, rows_per_query):
+    """row_ptr and the flat positions of a batch whose query q has the rows per_node[qi[q]] (a list
+    of rows_per_query arrays each): np.cumsum over the row lengths, np.repeat over the rows."""
+    lens = np.array([[len(r) for r in rows] for rows in per_node], np.int64)           # (nodes, R)
+    flat = np.concatenate([np.asarray(r, np.uint64) for rows in per_node for r in rows] + [np.zeros(0, np.uint64)])
+    start = np.concatenate([[0], np.cumsum(lens.reshape(-1))])[:-1].reshape(lens.shape)  # of each row in flat
+    row_len, row_start = lens[qi].reshape(-1), start[qi].reshape(-1)
+    assert row_len.shape == (len(qi) * rows_per_query,)
+    row_ptr = np.concatenate([[0], np.cumsum(row_len)])
+    src = np.repeat(row_start - row_ptr[:-1], row_len) + np.arange(row_ptr[-1])
+    return row_ptr, flat[src]
+
+
+def _cycle(n, nq):
+    """nq queries cycling over positions 0 .. n (n itself out of range: empty rows at the block
+    edges, 2048 and n + 1 being coprime), the last 3000 all out of range."""
+    qi = np.arange(nq) % (n + 1)
+    qi[-3000:] = n
+    return qi
+
+
+@pytest.mark.parametrize("min_count", [0, 1], ids=["plain", "filtered"])
+def test_at_batch_past_one_pass_of_the_block_sum_scan(tiny, min_count):
+    """2^21 + 2049 + 5 DESC_AT rows: k_rows_top carries its running sum into a second pass of 1024
+    block sums; with the filter k_desc_filter<kRows> writes as many row_ptr entries, thousands
+    of them for rows that start at `total`."""
+    arr, n = tiny.arr, tiny.n
+    per = [_at(arr, p, 1) for p in range(n + 1)]
+    for p in range(n + 1):
+        assert _same_row(per[p], _q_at(arr, p, 1)), p
+    assert sorted({len(r) for r in per if r is not None}) == [0, 1, 2, 3] and per[n] is None
+    kept = [_filtered(r, tiny.stats, min_count, 0) for r in per]
+    assert min_count == 0 or 0 < sum(len(r) for r in kept if r is not None) < sum(len(r) for r in per if r is not None)
+    nq = SCAN_PASS + SCAN_BLOCK + 1 + 5
+    qi = _cycle(n, nq)
+    row_ptr, out = _expand([[r if r is not None else []] for r in kept], qi, 1)
+    levels, got_rp, got = tiny.idx.descendants_csr(qi.astype(np.uint64), 1, 0, min_count, 0)
+    assert np.array_equal(levels.cpu().numpy(), np.array([r is not None for r in per], np.int32)[qi])
+    assert np.array_equal(got_rp.cpu().numpy(), row_ptr)
+    assert row_ptr[-1] == row_ptr[-3000] and np.array_equal(got.cpu().numpy().view(np.uint64), out)
+
+
+def test_upto_batch_past_one_pass_of_the_block_sum_scan(tiny):
+    """DESC_UPTO with three rows per query crosses the same bound with a third of the queries."""
+    arr, n, R = tiny.arr, tiny.n, 3
+    per = [_upto(arr, p, R) for p in range(n + 1)]
+    for p in range(n + 1):
+        _check_upto([per[p]], [_q_upto(arr, p, R)], "tiny UPTO %d" % p)
+    nq = SCAN_PASS // R + 700
+    assert nq * R > SCAN_PASS + SCAN_BLOCK
+    qi = _cycle(n, nq)
+    rows = [list(r or []) + [[]] * (R - len(r or [])) for r in per]
+    row_ptr, out = _expand(rows, qi, R)
+    levels, got_rp, got = tiny.idx.descendants_csr(qi.astype(np.uint64), None, R)
+    assert np.array_equal(levels.cpu().numpy(), np.array([len(r or []) for r in per], np.int32)[qi])
+    assert max(len(r or []) for r in per) == 2 and np.array_equal(got_rp.cpu().numpy(), row_ptr)
+    assert np.array_equal(got.cpu().numpy().view(np.uint64), out)
+
+
 def test_attach_and_end_to_end(s3, big, tmp_path):
     """Index.from_arrays over the device build's and the device finalize's tensors, then the
     whole pipeline through files: builder, finalize, stats, manifest, Open."""
