@@ -2333,7 +2333,7 @@ bool reclaim_cached(s3imph_ctx* keep, const void* keep_set) {
       if (!c || c == keep) continue;
       std::unique_lock<std::mutex> lk(c->mu, std::try_to_lock);
       if (!lk.owns_lock()) continue;  // building right now
-      if (!c->hist && !c->s_blob && !c->fin && !c->agg) continue;  // nothing cached
+      if (!c->hist && !c->s_blob && !c->fin && !c->agg && !c->srt && !c->csv && !c->mrg) continue;  // nothing cached
       (void)hipSetDevice(c->device);
       if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
       free_workspace(c);
@@ -2347,7 +2347,7 @@ bool reclaim_cached(s3imph_ctx* keep, const void* keep_set) {
       any = true;
     }
   }
-  if (keep && (keep->fin || keep->agg || keep->srt || keep->csv)) {
+  if (keep && (keep->fin || keep->agg || keep->srt || keep->csv || keep->mrg)) {
     fin_scratch_free(keep);
     agg_scratch_free(keep);
     sort_scratch_free(keep);

@@ -1228,9 +1228,15 @@ def merge_geometry() -> int:
 
 def _row_runs(runs):
     """Runs as (blob, offsets, depth, count, bytes[, tier_count, tier_bytes[, mask]]) tuples — the
-    tuples aggregate() returns — -> (RowRun array, k, the arrays kept alive)."""
+    tuples aggregate() returns — -> (RowRun array, k, the arrays kept alive).  A run may also be a
+    RowRun the caller has filled (any offsets[0], any tier_stride, NULL pointers): it is passed as
+    it is, and the caller keeps its arrays alive."""
     keep, out = [], []
     for run in runs:
+        if isinstance(run, RowRun):
+            keep.append(run)
+            out.append(run)
+            continue
         run = tuple(run)
         if len(run) not in (5, 7, 8):
             raise ValueError("a run is (blob, offsets, depth, count, bytes[, tier_count, tier_bytes])")
@@ -1286,7 +1292,7 @@ def merge_rows(runs, device: int = 0, with_info: bool = False):
         offsets = take(out[1], np.uint64, nn + 1)
         rows = (take(out[0], np.uint8, int(offsets[-1])), offsets, take(out[2], np.uint32, nn),
                 take(out[3], np.uint64, nn), take(out[4], np.uint64, nn))
-        if any(x[5] is not None and len(x[1]) > 1 for x in keep):
+        if any(arr[r].tier_count and arr[r].n for r in range(k)):  # an empty run counts with neither
             rows += (take(out[5], np.uint64, NUM_TIERS * nn).reshape(NUM_TIERS, nn),
                      take(out[6], np.uint64, NUM_TIERS * nn).reshape(NUM_TIERS, nn), int(mask.value))
         return rows + (info.as_dict(),) if with_info else rows

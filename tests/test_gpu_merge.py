@@ -1,10 +1,15 @@
 """The row merge on the GPU (include/s3imph.h section 5i) against tests/merge_ref.py: all seven
 outputs — blob, offsets, depth, count, bytes, tier counts, tier bytes — compared exactly, through
-the device plan / fill and through merge_rows (the host call, with its rounds past 64 runs)."""
+the device plan / fill and through merge_rows (the host call, with its rounds past 64 runs, up to
+three levels of them, and with runs in every memory layout s3imph_row_run allows); the byte emit
+on its 2048-byte chunk edges."""
+import time
+
 import numpy as np
 import pytest
 
 import merge_ref as M
+import rowset_cases as RC
 import s3imph
 import tiers_ref as T
 
@@ -336,3 +341,170 @@ def test_200k_rows_in_7_runs_of_unequal_size(ctx):
     assert sum(len(r) for r in runs) == 200_000
     want = check(ctx, runs, what="200k")
     assert len(want) < 120_000
+
+
+# ---- the host merge in the run layouts the header allows (tests/rowset_cases.py) ----------------
+def host_merge(runs, tiers, what):
+    """merge_rows over RowRuns or tuples: (the 7 or 5 arrays, the mask or None, info)."""
+    out = s3imph.merge_rows(runs, with_info=True)
+    assert len(out) == (9 if tiers else 6), what
+    return list(out[:7 if tiers else 5]), (out[7] if tiers else None), out[-1]
+
+
+@pytest.mark.parametrize("tiers", [True, False], ids=["tiers", "no tiers"])
+@pytest.mark.parametrize("k", [5, 65])
+def test_merge_rows_in_every_layout(k, tiers):
+    """Bases 1, 5, 8, 13 with junk around the keys, tier_stride n + 3 with junk in the slack, a
+    root-only run with a NULL blob, empty runs (NULL and not) first, in the middle and last; with
+    k = 65 the laid-out runs also pass through the first round's download and come back as the
+    second round's runs."""
+    parts = RC.part_rows(k)
+    runs = parts[:k // 2] + [RC.ROOT_ONLY] + parts[k // 2:]
+    logical, laid = RC.layouts(runs, tiers)
+    assert len(laid) == k + 7 and (k < 64 or len(laid) > 64)
+    want_rows = M.merge_heap(logical)
+    assert want_rows == M.merge_heap(runs) and len(want_rows) == len(RC.whole_rows("shapes"))
+    want = M.to_arrays(want_rows)[:7 if tiers else 5]
+    got, mask, info = host_merge(laid, tiers, "laid out")
+    same(got, want, f"k={k} laid out")
+    packed, pmask, pinfo = host_merge([M.to_arrays(r)[:7 if tiers else 5] for r in logical], tiers, "packed")
+    same(packed, want, f"k={k} packed")
+    assert mask == pmask == (M.present_mask(want_rows) if tiers else None)
+    assert info == pinfo and info["n_in"] == sum(len(r) for r in runs) and info["n_out"] == len(want_rows)
+    assert info["first_unsorted"] == NONE and info["max_depth_seen"] == max(r[1] for r in want_rows)
+
+
+@pytest.mark.parametrize("base", [1, 5, 8, 13])
+def test_one_run_with_a_base_is_the_identity(base):
+    """A single run whose offsets start at `base`: the rebasing alone, no second run to hide behind."""
+    rows = RC.part_rows(5)[base % 5]
+    got, mask, info = host_merge([RC.layout_run(rows, base=base, stride_extra=base % 2)], True, f"base {base}")
+    same(got, M.to_arrays(rows), f"base {base}")
+    assert mask == M.present_mask(rows) and info["n_in"] == info["n_out"] == len(rows)
+
+
+def test_only_empty_runs_in_every_layout():
+    _, laid = RC.layouts([], True)
+    out = s3imph.merge_rows(laid, with_info=True)
+    assert len(out) == 6 and out[1].tolist() == [0] and len(out[0]) == 0 and out[-1]["n_out"] == 0
+
+
+def test_an_unsorted_run_in_a_layout_is_reported_at_its_row():
+    parts = RC.part_rows(5)
+    bad = parts[2][:10] + [parts[2][11], parts[2][10]] + parts[2][12:]
+    runs = parts[:2] + [bad] + parts[3:]
+    _, laid = RC.layouts(runs, True)
+    with pytest.raises(s3imph.MPHFError) as e:
+        s3imph.merge_rows(laid)
+    assert e.value.status == s3imph.ERR_INVALID and str(e.value).startswith("merge: ")
+    assert e.value.info["first_unsorted"] == M.first_unsorted(runs) == len(parts[0]) + len(parts[1]) + 11
+
+
+# ---- rounds --------------------------------------------------------------------------------------
+def test_an_empty_group_of_64_runs():
+    """130 runs, runs 64..127 without a row (NULL pointers and real empty arrays alternating): the
+    first round's second group yields an empty run for the second round."""
+    parts = RC.part_rows(66)
+    hole = [RC.layout_run([], null=True) if r % 2 else RC.layout_run([], base=5) for r in range(64)]
+    runs = [M.to_arrays(r) for r in parts[:64]] + hole + [M.to_arrays(r) for r in parts[64:]]
+    got, mask, info = host_merge(runs, True, "hole")
+    want_rows = RC.whole_rows("shapes")
+    same(got, M.to_arrays(want_rows), "130 runs, 64 of them empty")
+    assert mask == M.present_mask(want_rows)
+    assert info["n_in"] == sum(len(r) for r in parts) and info["n_out"] == len(want_rows) and info["n_runs"] == 130
+
+
+def test_the_smallest_unsorted_row_over_two_groups():
+    """130 runs, an unsorted run in group 0 and another in group 1: the smallest index is reported,
+    as an index into the concatenation of all runs."""
+    runs = [rows_of([b"r/%04d/" % (3 * r), b"r/%04d/" % (3 * r + 4)], base=10 * r + 1) for r in range(130)]
+    runs[5], runs[100] = runs[5][::-1], runs[100][::-1]
+    with pytest.raises(s3imph.MPHFError) as e:
+        s3imph.merge_rows([M.to_arrays(run) for run in runs])
+    assert e.value.status == s3imph.ERR_INVALID and str(e.value).startswith("merge: ")
+    assert e.value.info["first_unsorted"] == M.first_unsorted(runs) == 11
+    assert e.value.info["n_in"] == 260
+    runs[5] = runs[5][::-1]  # only group 1 is left unsorted
+    with pytest.raises(s3imph.MPHFError) as e:
+        s3imph.merge_rows([M.to_arrays(run) for run in runs])
+    assert e.value.info["first_unsorted"] == M.first_unsorted(runs) == 201
+
+
+def test_4097_runs_take_three_rounds():
+    """64 * 64 + 1 runs of one or two rows, no tier columns: 65 groups, then 2, then the last merge.
+    One key sits in run 0, run 2048 and run 4096 with three depths; run 0's wins.  The call takes
+    about 0.4 s on an MI355X (printed)."""
+    k = 64 * 64 + 1
+    runs = []
+    for r in range(k):
+        keys = [b"t/%05d/" % (2 * r)] + ([b"t/%05d/" % (2 * r + 4)] if r % 3 else [])
+        runs.append([M.row(key, 2, r + 1, 10 * r + i) for i, key in enumerate(keys)])
+    for r, d in ((0, 4), (2048, 7), (4096, 9)):
+        runs[r] = [M.row(b"same/", d, 100 + r, r)] + runs[r]
+    want_rows = M.merge_heap(runs)
+    (row,) = [r for r in want_rows if r[0] == b"same/"]
+    assert row[1:4] == (4, 300 + 2048 + 4096, 2048 + 4096)
+    assert len(want_rows) < sum(len(r) for r in runs)  # t/%05d/ keys of neighbouring runs coincide
+    arrays = [M.to_arrays(run)[:5] for run in runs]
+    t0 = time.perf_counter()
+    out = s3imph.merge_rows(arrays, with_info=True)
+    took = time.perf_counter() - t0
+    print(f"4097 runs through merge_rows: {took:.2f} s")
+    assert len(out) == 6
+    same(out[:5], M.to_arrays(want_rows)[:5], "K=4097")
+    info = out[-1]
+    assert info["n_in"] == sum(len(r) for r in runs) and info["n_out"] == len(want_rows)
+    assert info["first_unsorted"] == NONE and info["max_depth_seen"] == 4 and info["present_mask"] == 0
+
+
+# ---- the byte emit at its 2048-byte chunk edges --------------------------------------------------
+EMIT_CHUNK = 8 * 256  # k_merge_bytes: one 8-byte word per lane, 256 lanes per workgroup
+
+
+def emit_runs(lengths):
+    """Rows with the given key lengths in output order (distinct, byte-sorted by their first byte),
+    dealt over three runs so that neighbouring output rows come from different runs.  Two rows are
+    duplicated: the longest (it sits in run 1) also into run 0, so the head and its bytes come from
+    the copy; and row 3 (of run 0) also into run 1, so they come from the original."""
+    assert len(lengths) < 90
+    keys = [bytes([0x21 + i]) + bytes([0x61 + (i + j) % 26 for j in range(ln - 1)]) for i, ln in enumerate(lengths)]
+    assert keys == sorted(keys) and [len(k) for k in keys] == list(lengths)
+    rows = rows_of(keys)
+    runs = [rows[0::3], rows[1::3], rows[2::3]]
+    big = max(range(len(keys)), key=lambda i: lengths[i])
+    assert big % 3 == 1 and big != 3
+    for i, r in ((big, 0), (3, 1)):
+        runs[r] = sorted(runs[r] + [M.row(keys[i], 50, 7, 7, {3: (7, 7)})], key=lambda x: x[0])
+    return runs, keys
+
+
+EMIT_LAYOUTS = {
+    # 1, 2, 3: three rows inside the first word; 1..9 bytes; a row ending at byte 2048; a key of 4200
+    # bytes owning chunk [4096, 6144) and the start of the next; a total of 6253 = 5 mod 8
+    "edges": [1, 2, 3, 4, 5, 6, 7, 8, 9, 2003, 4200, 3, 2],
+    "2048": [1, 2, 3, 9, 2033],
+    "2049": [1, 2, 3, 9, 2033, 1],
+}
+
+
+@pytest.mark.parametrize("name", EMIT_LAYOUTS)
+def test_merged_bytes_at_the_emit_chunk_edges(ctx, name):
+    lengths = EMIT_LAYOUTS[name]
+    runs, keys = emit_runs(lengths)
+    want_rows = M.merge_heap(runs)
+    assert [r[0] for r in want_rows] == keys and sum(len(r) for r in runs) == len(keys) + 2
+    offs = M.to_arrays(want_rows)[1].tolist()
+    # neighbouring output rows come from different runs, but for the one head moved into run 0
+    owner = [min(r for r in range(3) if any(x[0] == key for x in runs[r])) for key in keys]
+    assert sum(a == b for a, b in zip(owner, owner[1:])) <= 1 and set(owner) == {0, 1, 2}
+    heads = {r[0]: r[1] for r in want_rows}
+    assert sorted(d for d in heads.values() if d == 50) == [50]  # one head is the copy, the other the original
+    if name == "edges":
+        assert offs[:4] == [0, 1, 3, 6] and offs[10] == EMIT_CHUNK and offs[11] == EMIT_CHUNK + 4200
+        assert offs[11] > 3 * EMIT_CHUNK and offs[11] % EMIT_CHUNK != 0 and offs[-1] == 6253 and offs[-1] % 8 == 5
+        assert [b - a for a, b in zip(offs, offs[1:])][:9] == list(range(1, 10))
+    else:
+        assert offs[-1] == int(name) and offs[5] == EMIT_CHUNK
+    for align in range(1, 8):
+        check(ctx, runs, host=False, align=align, off0=5, what=f"{name} align {align}")
+    check(ctx, runs, tiers=False, host=True, align=3, off0=5, what=f"{name} no tiers")
