@@ -28,12 +28,10 @@
 // one scan turns the 24 columns of tile sums into wrapping prefixes, and the emit — one lane per
 // row, adjacent lanes adjacent rows, 24 coalesced column writes — takes the whole tiles of [i, e)
 // from the table and walks the two partial tiles (fewer than 2 kTG elements, whatever e - i is).
-#include <sys/stat.h>
-
 #include <cstdlib>
 #include <cstring>
 
-#include "s3imph_ctx.h"
+#include "s3imph_entry.h"
 #include "s3imph_keys.h"
 #include "s3imph_prim.h"
 #include "s3imph_tiers.h"
@@ -782,22 +780,6 @@ int rows_from_host(s3imph_ctx* c, DevGuard& g, const uint8_t* keys, const uint64
   return rc;
 }
 
-namespace {
-
-template <typename T>
-T* host_array(uint64_t count) {
-  T* p = static_cast<T*>(std::malloc(std::max<uint64_t>(count, 1) * sizeof(T)));
-  if (!p) throw std::bad_alloc();
-  return p;
-}
-
-bool is_dir(const std::string& p) {
-  struct stat st;
-  return ::stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
-}
-
-}  // namespace
-
 }  // namespace s3imph
 
 using namespace s3imph;
@@ -809,76 +791,43 @@ int s3imph_aggregate_plan_tiers_device(s3imph_ctx* c, const uint8_t* d_keys, con
                                        uint32_t max_depth, s3imph_agg_info* info, s3imph_agg_tier_info* tier_info,
                                        void* stream) {
   if (!c || !info || !tier_info || (m && (!d_keys || !d_key_offsets || !d_tiers))) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = retry_on_nomem(c, s, &msg, [&] {
+  return device_entry(c, "", [&](std::string& msg) {
+    hipStream_t s = use_device(c->device, stream, c->own_stream);
+    return retry_on_nomem(c, s, &msg, [&] {
       return aggregate_plan_tiers(c, d_keys, d_key_offsets, d_sizes, d_tiers, m, max_depth, info, tier_info, s, &msg);
     });
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_aggregate_fill_tiers_device(s3imph_ctx* c, uint64_t* d_tier_count, uint64_t* d_tier_bytes, uint64_t n_cap,
                                        void* stream) {
   if (!c) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = aggregate_fill_tiers(c, d_tier_count, d_tier_bytes, n_cap, s, &msg);
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = f.msg;
-    return f.code;
-  }
+  return device_entry(c, "", [&](std::string& msg) {
+    hipStream_t s = use_device(c->device, stream, c->own_stream);
+    return aggregate_fill_tiers(c, d_tier_count, d_tier_bytes, n_cap, s, &msg);
+  });
 }
 
 int s3imph_aggregate_plan_device(s3imph_ctx* c, const uint8_t* d_keys, const uint64_t* d_key_offsets,
                                  const uint64_t* d_sizes, uint64_t m, uint32_t max_depth, s3imph_agg_info* info,
                                  void* stream) {
   if (!c || !info || (m && (!d_keys || !d_key_offsets))) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = retry_on_nomem(c, s, &msg, [&] {
+  return device_entry(c, "", [&](std::string& msg) {
+    hipStream_t s = use_device(c->device, stream, c->own_stream);
+    return retry_on_nomem(c, s, &msg, [&] {
       return aggregate_plan(c, d_keys, d_key_offsets, d_sizes, m, max_depth, info, s, &msg);
     });
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_aggregate_fill_device(s3imph_ctx* c, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offsets,
                                  uint32_t* d_depth, uint64_t* d_object_count, uint64_t* d_total_bytes,
                                  uint64_t n_cap, void* stream) {
   if (!c) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = aggregate_fill(c, d_blob, blob_cap, d_offsets, d_depth, d_object_count, d_total_bytes, n_cap, s,
-                                  &msg);
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = f.msg;
-    return f.code;
-  }
+  return device_entry(c, "", [&](std::string& msg) {
+    hipStream_t s = use_device(c->device, stream, c->own_stream);
+    return aggregate_fill(c, d_blob, blob_cap, d_offsets, d_depth, d_object_count, d_total_bytes, n_cap, s, &msg);
+  });
 }
 
 // s3imph_aggregate_host, and with `tiers` s3imph_aggregate_tiers_host (tier_count, tier_bytes and
@@ -890,90 +839,20 @@ static int aggregate_host_impl(int device, const uint8_t* keys, const uint64_t* 
                                char* err, size_t errlen) {
   if (!blob || !offsets || !depth || !object_count || !total_bytes || !n || !listing_given(keys, key_offsets, m))
     return S3IMPH_ERR_INVALID;
-  uint64_t *no_count = nullptr, *no_bytes = nullptr, no_mask = 0;
-  if (!tiers) {
-    tier_count = &no_count;
-    tier_bytes = &no_bytes;
-    present_mask = &no_mask;
-  }
-  *blob = nullptr;
-  *offsets = nullptr;
-  *depth = nullptr;
-  *object_count = *total_bytes = nullptr;
-  *tier_count = *tier_bytes = nullptr;
-  *present_mask = 0;
-  *n = 0;
-  std::string msg;
-  auto drop = [&] {
-    std::free(*blob);
-    std::free(*offsets);
-    std::free(*depth);
-    std::free(*object_count);
-    std::free(*total_bytes);
-    std::free(*tier_count);
-    std::free(*tier_bytes);
-    *blob = nullptr;
-    *offsets = nullptr;
-    *depth = nullptr;
-    *object_count = *total_bytes = nullptr;
-    *tier_count = *tier_bytes = nullptr;
-  };
-  try {
-    if (m == 0) {  // Drain returns nil
-      *offsets = host_array<uint64_t>(1);
-      (*offsets)[0] = 0;
-      return S3IMPH_OK;
-    }
-    s3imph_ctx* c = default_ctx(device, &msg);
-    if (!c) {
-      set_err(err, errlen, "aggregate: " + msg);
-      return S3IMPH_ERR_HIP;
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHECK(hipSetDevice(c->device));
-    const int rc = retry_on_nomem(c, c->own_stream, &msg, [&] {
-      DevGuard g;
-      DevRows r;
-      const int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers);
-      if (rc2 != S3IMPH_OK) return rc2;
-      drop();
-      *blob = host_array<uint8_t>(r.blob_bytes);
-      *offsets = host_array<uint64_t>(r.n + 1);
-      *depth = host_array<uint32_t>(r.n);
-      *object_count = host_array<uint64_t>(r.n);
-      *total_bytes = host_array<uint64_t>(r.n);
-      if (r.blob_bytes) HIPCHECK(hipMemcpy(*blob, r.blob, r.blob_bytes, hipMemcpyDeviceToHost));
-      staged_copy(c, false, *offsets, r.offsets, (r.n + 1) * 8);
-      staged_copy(c, false, *depth, r.depth, r.n * 4);
-      staged_copy(c, false, *object_count, r.ocnt, r.n * 8);
-      staged_copy(c, false, *total_bytes, r.tbytes, r.n * 8);
-      if (tiers) {
-        *tier_count = host_array<uint64_t>(kNT * r.n);
-        *tier_bytes = host_array<uint64_t>(kNT * r.n);
-        staged_copy(c, false, *tier_count, r.tier_count, kNT * r.n * 8);
-        staged_copy(c, false, *tier_bytes, r.tier_bytes, kNT * r.n * 8);
-        *present_mask = r.present_mask;
-      }
-      *n = r.n;
-      return (int)S3IMPH_OK;
-    });
-    if (rc != S3IMPH_OK) {
-      drop();
-      *n = 0;
-      set_err(err, errlen, msg);
-    }
-    return rc;
-  } catch (const Fail& f) {
-    drop();
-    *n = 0;
-    set_err(err, errlen, "aggregate: " + f.msg);
-    return f.code;
-  } catch (const std::bad_alloc&) {
-    drop();
-    *n = 0;
-    set_err(err, errlen, "aggregate: out of host memory");
-    return S3IMPH_ERR_NOMEM;
-  }
+  HostRows out(blob, offsets, depth, object_count, total_bytes, tiers ? tier_count : nullptr,
+               tiers ? tier_bytes : nullptr, tiers ? present_mask : nullptr, n);
+  out.reset();
+  if (m == 0)  // Drain returns nil
+    return host_call("aggregate: ", err, errlen, [&](std::string&) { return out.none(); });
+  const int rc = host_entry(device, "aggregate: ", err, errlen, [&](s3imph_ctx* c, hipStream_t, std::string& msg) {
+    DevGuard g;
+    DevRows r;
+    const int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers);
+    if (rc2 == S3IMPH_OK) out.download(c, r, tiers != nullptr);
+    return rc2;
+  });
+  if (rc != S3IMPH_OK) out.drop();
+  return rc;
 }
 
 int s3imph_aggregate_host(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint64_t* sizes,
@@ -1027,17 +906,8 @@ int s3imph::index_arrays_from_rows(s3imph_ctx* c, DevGuard& g, DevRows& r, bool 
   g.make(d_dpos, n);
   g.make(d_depth, n);
   g.make(d_maxds, n);
-  uint64_t cap = 64;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    g.make(d_doff, cap);
-    rc2 = finalize_device(c, r.blob, r.offsets, r.depth, n, d_depth, d_send, d_maxds, d_dpos, d_doff, cap, &h.md,
-                          s, &msg);
-    if (rc2 == S3IMPH_OK) break;
-    if (rc2 != S3IMPH_ERR_INVALID || attempt) return rc2;
-    cap = (uint64_t)h.md + 2;
-    g.drop(d_doff);
-    d_doff = nullptr;
-  }
+  rc2 = finalize_rows(c, g, r.blob, r.offsets, r.depth, n, d_depth, d_send, d_maxds, d_dpos, d_doff, &h.md, s, &msg);
+  if (rc2 != S3IMPH_OK) return rc2;
   HIPCHECK(hipStreamSynchronize(s));
   uint64_t mlen = 0;
   h.mph.resize(binfo.mph_bin_len);
@@ -1099,48 +969,28 @@ int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* 
     set_err(err, errlen, "create mph file: open " + dir + "/mph.bin: no such directory");
     return S3IMPH_ERR_IO;
   }
-  std::string msg;
-  try {
-    IndexHostArrays h;
-    uint64_t csv_bytes = 0;
-    for (uint64_t i = 0; csv && i < csv->n_files; ++i) csv_bytes += csv->len[i];
-    if (m || csv_bytes) {
-      s3imph_ctx* c = default_ctx(device, &msg);
-      if (!c) {
-        set_err(err, errlen, (csv ? "csv: " : "aggregate: ") + msg);
-        return S3IMPH_ERR_HIP;
-      }
-      std::lock_guard<std::mutex> lk(c->mu);
-      HIPCHECK(hipSetDevice(c->device));
-      hipStream_t s = c->own_stream;
-      // one device residency: the rows stay in HBM from the aggregation to the last array
-      const int rc = retry_on_nomem(c, s, &msg, [&]() -> int {
-        DevGuard g;
-        DevRows r;
-        int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers, unsorted, csv);
-        if (rc2 != S3IMPH_OK) return rc2;
-        h.n = r.n;
-        if (r.m == 0) return S3IMPH_OK;  // CSV text without an object: the empty index below
-        return index_arrays_from_rows(c, g, r, tiers != nullptr, h, s, &msg);
-      });
-      if (rc != S3IMPH_OK) {
-        set_err(err, errlen, msg);
-        return rc;
-      }
-    }
-    const int rc = write_index_dir(dir, h, tiers != nullptr, &msg);
-    if (rc != S3IMPH_OK) set_err(err, errlen, msg);
-    return rc;
-  } catch (const Fail& f) {
-    // a failure inside the sort stage comes worded "sort: ..." (rows_from_host)
-    // and one inside the CSV parse "csv: ..."
-    set_err(err, errlen,
-            f.msg.compare(0, 6, "sort: ") == 0 || f.msg.compare(0, 5, "csv: ") == 0 ? f.msg : "aggregate: " + f.msg);
-    return f.code;
-  } catch (const std::bad_alloc&) {
-    set_err(err, errlen, "aggregate: out of host memory");
-    return S3IMPH_ERR_NOMEM;
+  const bool with_tiers = tiers != nullptr;
+  IndexHostArrays h;
+  uint64_t csv_bytes = 0;
+  for (uint64_t i = 0; csv && i < csv->n_files; ++i) csv_bytes += csv->len[i];
+  if (m || csv_bytes) {
+    // one device residency: the rows stay in HBM from the aggregation to the last array
+    const int rc = host_entry(
+        device, "aggregate: ", err, errlen,
+        [&](s3imph_ctx* c, hipStream_t s, std::string& msg) -> int {
+          DevGuard g;
+          DevRows r;
+          const int rc2 = rows_from_host(c, g, keys, key_offsets, sizes, m, max_depth, &r, &msg, tiers, unsorted, csv);
+          if (rc2 != S3IMPH_OK) return rc2;
+          h.n = r.n;
+          if (r.m == 0) return S3IMPH_OK;  // CSV text without an object: the empty index below
+          return index_arrays_from_rows(c, g, r, with_tiers, h, s, &msg);
+        },
+        csv ? "csv: " : nullptr);
+    if (rc != S3IMPH_OK) return rc;
   }
+  return host_call("aggregate: ", err, errlen,
+                   [&](std::string& msg) { return write_index_dir(dir, h, with_tiers, &msg); });
 }
 
 extern "C" {

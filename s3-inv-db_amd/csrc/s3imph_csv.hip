@@ -24,6 +24,7 @@
 // correct and slow.
 #include <cstring>
 
+#include "s3imph_entry.h"
 #include "s3imph_keys.h"
 #include "s3imph_prim.h"
 #include "s3imph_tiers.h"
@@ -704,35 +705,19 @@ int s3imph_csv_plan_device(s3imph_ctx* c, const uint8_t* d_csv, uint64_t len, co
                            s3imph_csv_info* info, void* stream) {
   if (!c || !schema || !info || (len && !d_csv) || schema->key_col < 0 || schema->size_col < 0)
     return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = retry_on_nomem(c, s, &msg, [&] { return csv_plan(c, d_csv, len, *schema, info, s, &msg); });
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = "csv: " + f.msg;
-    return f.code;
-  }
+  return device_entry(c, "csv: ", [&](std::string& msg) {
+    hipStream_t s = use_device(c->device, stream, c->own_stream);
+    return retry_on_nomem(c, s, &msg, [&] { return csv_plan(c, d_csv, len, *schema, info, s, &msg); });
+  });
 }
 
 int s3imph_csv_fill_device(s3imph_ctx* c, uint8_t* d_keys, uint64_t keys_cap, uint64_t key_base,
                            uint64_t* d_key_offsets, uint64_t* d_sizes, uint8_t* d_tiers, void* stream) {
   if (!c) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = csv_fill(c, d_keys, keys_cap, key_base, d_key_offsets, d_sizes, d_tiers, s, &msg);
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = "csv: " + f.msg;
-    return f.code;
-  }
+  return device_entry(c, "csv: ", [&](std::string& msg) {
+    hipStream_t s = use_device(c->device, stream, c->own_stream);
+    return csv_fill(c, d_keys, keys_cap, key_base, d_key_offsets, d_sizes, d_tiers, s, &msg);
+  });
 }
 
 int s3imph_csv_parse_host(int device, const uint8_t* csv, uint64_t len, const s3imph_csv_schema* schema,
@@ -752,69 +737,43 @@ int s3imph_csv_parse_host(int device, const uint8_t* csv, uint64_t len, const s3
     *keys = *tiers = nullptr;
     *key_offsets = *sizes = nullptr;
   };
-  auto host_array = [](uint64_t bytes) {
-    void* p = std::malloc(std::max<uint64_t>(bytes, 1));
-    if (!p) throw std::bad_alloc();
-    return p;
-  };
-  std::string msg;
-  try {
-    if (len == 0) {  // no device
-      *key_offsets = static_cast<uint64_t*>(host_array(8));
+  if (len == 0)  // no device
+    return host_call("csv: ", err, errlen, [&](std::string&) {
+      *key_offsets = host_array<uint64_t>(1);
       (*key_offsets)[0] = 0;
       return S3IMPH_OK;
-    }
-    s3imph_ctx* c = default_ctx(device, &msg);
-    if (!c) {
-      set_err(err, errlen, "csv: " + msg);
-      return S3IMPH_ERR_HIP;
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = c->own_stream;
-    const int rc = retry_on_nomem(c, s, &msg, [&]() -> int {
-      DevGuard g;
-      uint8_t *d_csv = nullptr, *d_keys = nullptr, *d_tiers = nullptr;
-      uint64_t *d_off = nullptr, *d_sizes = nullptr;
-      g.make(d_csv, (len + 7) & ~7ull);
-      staged_copy(c, true, d_csv, csv, len);
-      int rc2 = csv_plan(c, d_csv, len, *schema, info, s, &msg);
-      if (rc2 != S3IMPH_OK) return rc2;
-      const uint64_t n = info->n_objects, cap = (info->key_bytes + 7) & ~7ull;
-      g.make(d_keys, cap);
-      g.make(d_off, n + 1);
-      g.make(d_sizes, n);
-      g.make(d_tiers, n);
-      rc2 = csv_fill(c, d_keys, cap, 0, d_off, d_sizes, d_tiers, s, &msg);
-      c->csv->have_plan = false;  // the text's copy goes away with this call
-      if (rc2 != S3IMPH_OK) return rc2;
-      drop();
-      *keys = static_cast<uint8_t*>(host_array(info->key_bytes));
-      *key_offsets = static_cast<uint64_t*>(host_array(8 * (n + 1)));
-      *sizes = static_cast<uint64_t*>(host_array(8 * n));
-      *tiers = static_cast<uint8_t*>(host_array(n));
-      if (info->key_bytes) HIPCHECK(hipMemcpy(*keys, d_keys, info->key_bytes, hipMemcpyDeviceToHost));
-      staged_copy(c, false, *key_offsets, d_off, (n + 1) * 8);
-      if (n) {
-        staged_copy(c, false, *sizes, d_sizes, n * 8);
-        HIPCHECK(hipMemcpy(*tiers, d_tiers, n, hipMemcpyDeviceToHost));
-      }
-      return S3IMPH_OK;
     });
-    if (rc != S3IMPH_OK) {
-      drop();
-      set_err(err, errlen, msg);
+  const int rc = host_entry(device, "csv: ", err, errlen, [&](s3imph_ctx* c, hipStream_t s, std::string& msg) -> int {
+    DevGuard g;
+    uint8_t *d_csv = nullptr, *d_keys = nullptr, *d_tiers = nullptr;
+    uint64_t *d_off = nullptr, *d_sizes = nullptr;
+    g.make(d_csv, (len + 7) & ~7ull);
+    staged_copy(c, true, d_csv, csv, len);
+    int rc2 = csv_plan(c, d_csv, len, *schema, info, s, &msg);
+    if (rc2 != S3IMPH_OK) return rc2;
+    const uint64_t n = info->n_objects, cap = (info->key_bytes + 7) & ~7ull;
+    g.make(d_keys, cap);
+    g.make(d_off, n + 1);
+    g.make(d_sizes, n);
+    g.make(d_tiers, n);
+    rc2 = csv_fill(c, d_keys, cap, 0, d_off, d_sizes, d_tiers, s, &msg);
+    c->csv->have_plan = false;  // the text's copy goes away with this call
+    if (rc2 != S3IMPH_OK) return rc2;
+    drop();
+    *keys = host_array<uint8_t>(info->key_bytes);
+    *key_offsets = host_array<uint64_t>(n + 1);
+    *sizes = host_array<uint64_t>(n);
+    *tiers = host_array<uint8_t>(n);
+    if (info->key_bytes) HIPCHECK(hipMemcpy(*keys, d_keys, info->key_bytes, hipMemcpyDeviceToHost));
+    staged_copy(c, false, *key_offsets, d_off, (n + 1) * 8);
+    if (n) {
+      staged_copy(c, false, *sizes, d_sizes, n * 8);
+      HIPCHECK(hipMemcpy(*tiers, d_tiers, n, hipMemcpyDeviceToHost));
     }
-    return rc;
-  } catch (const Fail& f) {
-    drop();
-    set_err(err, errlen, "csv: " + f.msg);
-    return f.code;
-  } catch (const std::bad_alloc&) {
-    drop();
-    set_err(err, errlen, "csv: out of host memory");
-    return S3IMPH_ERR_NOMEM;
-  }
+    return S3IMPH_OK;
+  });
+  if (rc != S3IMPH_OK) drop();
+  return rc;
 }
 
 int s3imph_index_from_csv_host(int device, const uint8_t* const* csv, const uint64_t* csv_len, uint64_t n_files,

@@ -387,6 +387,11 @@ int retry_on_nomem(s3imph_ctx* keep, hipStream_t s, std::string* msg, F&& f) {
 int finalize_device(s3imph_ctx* c, const uint8_t* blob, const uint64_t* offsets, const uint32_t* depths, uint64_t n,
                     uint32_t* depth, uint64_t* subtree_end, uint32_t* max_depth_sub, uint64_t* depth_positions,
                     uint64_t* depth_offsets, uint64_t doff_cap, uint32_t* max_depth, hipStream_t s, std::string* msg);
+// finalize_device with depth_offsets made here (owned by g), grown once when 64 entries are too few
+int finalize_rows(s3imph_ctx* c, DevGuard& g, const uint8_t* blob, const uint64_t* offsets, const uint32_t* depths,
+                  uint64_t n, uint32_t* depth, uint64_t* subtree_end, uint32_t* max_depth_sub,
+                  uint64_t* depth_positions, uint64_t*& depth_offsets, uint32_t* max_depth, hipStream_t s,
+                  std::string* msg);
 int finalize_from_host(int device, const uint8_t* blob, const uint64_t* offsets, const uint32_t* depths, uint64_t n,
                        const std::string& dir, std::string* msg);
 void fin_scratch_free(s3imph_ctx* c);

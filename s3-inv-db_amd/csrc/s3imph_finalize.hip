@@ -26,7 +26,7 @@
 // integer work, HBM-bound: ΣL·2 + 32 B per key for the pass over the keys.
 #include <rocprim/iterator/counting_iterator.hpp>
 
-#include "s3imph_ctx.h"
+#include "s3imph_entry.h"
 #include "s3imph_keys.h"
 #include "s3imph_prim.h"
 
@@ -478,6 +478,24 @@ int finalize_device(s3imph_ctx* c, const uint8_t* blob, const uint64_t* offsets,
   return S3IMPH_OK;
 }
 
+// finalize_device with room for 64 depth offsets (made here, owned by g), and once more with
+// max_depth + 2 when those were too few.  Does not wait for the stream.
+int finalize_rows(s3imph_ctx* c, DevGuard& g, const uint8_t* blob, const uint64_t* offsets, const uint32_t* depths,
+                  uint64_t n, uint32_t* depth, uint64_t* subtree_end, uint32_t* max_depth_sub,
+                  uint64_t* depth_positions, uint64_t*& depth_offsets, uint32_t* max_depth, hipStream_t s,
+                  std::string* msg) {
+  uint64_t cap = 64;
+  for (int attempt = 0;; ++attempt) {
+    g.make(depth_offsets, cap);
+    const int rc = finalize_device(c, blob, offsets, depths, n, depth, subtree_end, max_depth_sub, depth_positions,
+                                   depth_offsets, cap, max_depth, s, msg);
+    if (rc != S3IMPH_ERR_INVALID || attempt) return rc;
+    cap = (uint64_t)*max_depth + 2;
+    g.drop(depth_offsets);
+    depth_offsets = nullptr;
+  }
+}
+
 // Host-memory finalize: H2D of the prefix blob (and depths), the device pass, D2H, and the
 // five files in out_dir with the reference's S3ID framing.
 int finalize_from_host(int device, const uint8_t* blob, const uint64_t* offsets, const uint32_t* depths, uint64_t n,
@@ -504,18 +522,10 @@ int finalize_from_host(int device, const uint8_t* blob, const uint64_t* offsets,
         g.make(d_din, n);
         HIPCHECK(hipMemcpy(d_din, depths, n * 4, hipMemcpyHostToDevice));
       }
-      uint64_t cap = 64;
       uint32_t md = 0;
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        g.make(d_doff, cap);
-        int rc = finalize_device(c, d_blob, d_offs, d_din, n, d_depth, d_send, d_maxds, d_dpos, d_doff, cap, &md, s,
-                                 msg);
-        if (rc == S3IMPH_OK) break;
-        if (rc != S3IMPH_ERR_INVALID || attempt) return rc;
-        cap = (uint64_t)md + 2;
-        g.drop(d_doff);
-        d_doff = nullptr;
-      }
+      const int rc =
+          finalize_rows(c, g, d_blob, d_offs, d_din, n, d_depth, d_send, d_maxds, d_dpos, d_doff, &md, s, msg);
+      if (rc != S3IMPH_OK) return rc;
       doff.resize((uint64_t)md + 2);
       HIPCHECK(hipStreamSynchronize(s));
       HIPCHECK(hipMemcpy(doff.data(), d_doff, doff.size() * 8, hipMemcpyDeviceToHost));
@@ -561,20 +571,13 @@ int s3imph_finalize_index_device(s3imph_ctx* c, const uint8_t* d_blob, const uin
   if (!c || !max_depth || !d_depth_offsets ||
       (n && (!d_blob || !d_offsets || !d_depth || !d_subtree_end || !d_max_depth_in_subtree || !d_depth_positions)))
     return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    int rc = finalize_device(c, d_blob, d_offsets, d_depths, n, d_depth, d_subtree_end, d_max_depth_in_subtree,
-                             d_depth_positions, d_depth_offsets, offsets_cap, max_depth, s, &msg);
+  return device_entry(c, "", [&](std::string& msg) {
+    hipStream_t s = use_device(c->device, stream, c->own_stream);
+    const int rc = finalize_device(c, d_blob, d_offsets, d_depths, n, d_depth, d_subtree_end, d_max_depth_in_subtree,
+                                   d_depth_positions, d_depth_offsets, offsets_cap, max_depth, s, &msg);
     if (rc == S3IMPH_OK) HIPCHECK(hipStreamSynchronize(s));
-    c->last_msg = msg;
     return rc;
-  } catch (const Fail& f) {
-    c->last_msg = f.msg;
-    return f.code;
-  }
+  });
 }
 
 }  // extern "C"

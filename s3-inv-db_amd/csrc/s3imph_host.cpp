@@ -177,12 +177,12 @@ bool write_raw(const std::string& path, const uint8_t* p, uint64_t n, std::strin
   return true;
 }
 
+}  // namespace
+
 bool is_dir(const std::string& p) {
   struct stat st;
   return ::stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
 }
-
-}  // namespace
 
 // EncodeHeader (format.go:25-32): magic, version, count, width — little endian, 20 bytes.
 void s3id_header(uint8_t out[kS3idHeaderSize], uint64_t count, uint32_t width) {

@@ -31,7 +31,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "s3imph_ctx.h"
+#include "s3imph_entry.h"
 #include "s3imph_keys.h"
 #include "s3imph_pricing.h"
 #include "s3imph_prim.h"
@@ -759,6 +759,15 @@ struct s3imph_index {
 namespace s3imph {
 namespace {
 
+// A device call on the index: the device frame, with the last message cleared on entry.
+template <class F>
+int index_entry(s3imph_index* x, F&& body) {
+  return device_entry(x, "", [&](std::string& msg) -> int {
+    x->last_msg.clear();
+    return body(msg);
+  });
+}
+
 void index_free(s3imph_index* x) {
   if (!x) return;
   (void)hipSetDevice(x->device);
@@ -836,7 +845,7 @@ void ensure_chunks(s3imph_index* x, uint64_t chunks) {
 
 int plan_locked(s3imph_index* x, const uint64_t* d_qpos, const int32_t* d_rel, uint64_t nq, int mode, int32_t max_rel,
                 uint64_t min_count, uint64_t min_bytes, int32_t* d_levels, uint64_t* d_row_ptr, uint64_t row_ptr_cap,
-                uint64_t* n_rows, uint64_t* total, hipStream_t s) {
+                uint64_t* n_rows, uint64_t* total, hipStream_t s, std::string* msg) {
   const bool upto = mode == S3IMPH_DESC_UPTO, filtered = min_count || min_bytes;
   const uint64_t R = upto ? std::min<uint64_t>(max_rel > 0 ? (uint64_t)max_rel : 0, x->a.max_depth) : 1;
   x->have_plan = false;
@@ -847,12 +856,12 @@ int plan_locked(s3imph_index* x, const uint64_t* d_qpos, const int32_t* d_rel, u
     return S3IMPH_OK;
   }
   if (R && nq > ((1ull << 31) - 1) / R) {
-    x->last_msg = "descendants plan: 2^31 result rows or more in one batch";
+    *msg = "descendants plan: 2^31 result rows or more in one batch";
     return S3IMPH_ERR_INVALID;
   }
   const uint64_t rows = nq * R;
   if (row_ptr_cap < rows + 1) {
-    x->last_msg = "descendants plan: row_ptr needs " + std::to_string(rows + 1) + " entries";
+    *msg = "descendants plan: row_ptr needs " + std::to_string(rows + 1) + " entries";
     return S3IMPH_ERR_INVALID;
   }
   *n_rows = rows;
@@ -880,7 +889,7 @@ int plan_locked(s3imph_index* x, const uint64_t* d_qpos, const int32_t* d_rel, u
     } else {
       const uint64_t chunks = (tu + kChunk - 1) / kChunk;
       if (chunks + 1 > 0x7fffffffull) {
-        x->last_msg = "descendants plan: more than 2^42 candidates in one batch";
+        *msg = "descendants plan: more than 2^42 candidates in one batch";
         return S3IMPH_ERR_INVALID;
       }
       ensure_chunks(x, chunks);
@@ -907,10 +916,10 @@ int plan_locked(s3imph_index* x, const uint64_t* d_qpos, const int32_t* d_rel, u
 }
 
 // The positions of the plan's rows into out (plan_total entries, > 0); the caller holds the lock.
-int fill_locked(s3imph_index* x, uint64_t* out, const char* what, hipStream_t s) {
+int fill_locked(s3imph_index* x, uint64_t* out, const char* what, hipStream_t s, std::string* msg) {
   const uint64_t tu = x->plan_total_u, chunks = (tu + kChunk - 1) / kChunk;
   if (chunks > 0x7fffffffull) {
-    x->last_msg = std::string(what) + ": more than 2^42 positions in one batch";
+    *msg = std::string(what) + ": more than 2^42 positions in one batch";
     return S3IMPH_ERR_INVALID;
   }
   if (x->plan_filtered)
@@ -923,7 +932,7 @@ int fill_locked(s3imph_index* x, uint64_t* out, const char* what, hipStream_t s)
 }
 
 int top_locked(s3imph_index* x, int key, const s3imph_price_table& pt, uint32_t k, uint64_t* d_top_pos,
-               uint64_t* d_top_key, uint32_t* d_top_n, hipStream_t s) {
+               uint64_t* d_top_key, uint32_t* d_top_n, hipStream_t s, std::string* msg) {
   const uint64_t rows = x->plan_rows, total = x->plan_total;
   if (rows == 0) return S3IMPH_OK;
   const uint64_t* rp = nullptr;
@@ -933,7 +942,7 @@ int top_locked(s3imph_index* x, int key, const s3imph_price_table& pt, uint32_t 
     uint64_t *pos = x->top_buf, *keys = pos + total;
     spos = keys + total;
     skey = spos + total;
-    const int rc = fill_locked(x, pos, "descendants top", s);
+    const int rc = fill_locked(x, pos, "descendants top", s, msg);
     if (rc != S3IMPH_OK) return rc;
     if (x->plan_filtered) {  // the plan wrote the filtered row_ptr to the caller only: read it off again
       grow(x->top_rp, x->top_rp_cap, rows + 1);
@@ -1077,41 +1086,32 @@ int s3imph_index_lookup_device(s3imph_index* x, const uint8_t* d_blob, const uin
 
 int s3imph_index_nodes_device(s3imph_index* x, const uint64_t* d_qpos, uint64_t nq, s3imph_node* d_out, void* stream) {
   if (!x || (nq && (!d_qpos || !d_out))) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(x->mu);
-  x->last_msg.clear();
-  if (nq == 0) return S3IMPH_OK;
-  try {
-    HIPCHECK(hipSetDevice(x->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+  return index_entry(x, [&](std::string&) -> int {
+    if (nq == 0) return S3IMPH_OK;
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
     k_index_nodes<<<(unsigned)((nq + kQT - 1) / kQT), kQT, 0, s>>>(x->a, d_qpos, nq, d_out);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     return S3IMPH_OK;
-  } catch (const Fail& f) {
-    x->last_msg = f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_index_attach_tiers(s3imph_index* x, const uint8_t* ids, uint64_t T, const uint64_t* d_tier_count,
                               const uint64_t* d_tier_bytes, uint64_t stride) {
   if (!x) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(x->mu);
-  x->last_msg.clear();
-  unsigned seen = 0;
-  bool ok = T <= (uint64_t)S3IMPH_NUM_TIERS && (T == 0 || ids) && stride >= x->a.n &&
-            (T == 0 || x->a.n == 0 || (d_tier_count && d_tier_bytes));
-  for (uint64_t k = 0; ok && k < T; ++k) {
-    ok = ids[k] < S3IMPH_NUM_TIERS && !((seen >> ids[k]) & 1);
-    seen |= 1u << (ids[k] & 31);
-  }
-  if (!ok) {
-    x->last_msg = "attach tiers: invalid argument";
-    return S3IMPH_ERR_INVALID;
-  }
-  try {
-    HIPCHECK(hipSetDevice(x->device));
-    hipStream_t s = x->ctx->own_stream;
+  return index_entry(x, [&](std::string& msg) -> int {
+    unsigned seen = 0;
+    bool ok = T <= (uint64_t)S3IMPH_NUM_TIERS && (T == 0 || ids) && stride >= x->a.n &&
+              (T == 0 || x->a.n == 0 || (d_tier_count && d_tier_bytes));
+    for (uint64_t k = 0; ok && k < T; ++k) {
+      ok = ids[k] < S3IMPH_NUM_TIERS && !((seen >> ids[k]) & 1);
+      seen |= 1u << (ids[k] & 31);
+    }
+    if (!ok) {
+      msg = "attach tiers: invalid argument";
+      return S3IMPH_ERR_INVALID;
+    }
+    hipStream_t s = use_device(x->device, nullptr, x->ctx->own_stream);
     x->T = 0;
     dfree(x->tier_table);
     if (T == 0) return S3IMPH_OK;
@@ -1127,10 +1127,7 @@ int s3imph_index_attach_tiers(s3imph_index* x, const uint8_t* ids, uint64_t T, c
     std::memcpy(x->tier_ids, slots.id, sizeof slots.id);
     x->T = (uint32_t)T;
     return S3IMPH_OK;
-  } catch (const Fail& f) {
-    x->last_msg = f.msg;
-    return f.code;
-  }
+  });
 }
 
 uint64_t s3imph_index_tier_count(const s3imph_index* x) { return x ? x->T : 0; }
@@ -1144,27 +1141,21 @@ uint64_t s3imph_index_tier_ids(const s3imph_index* x, uint8_t* ids, uint64_t cap
 int s3imph_index_tiers_device(s3imph_index* x, const uint64_t* d_qpos, uint64_t nq, uint64_t* d_out, uint32_t* d_mask,
                               void* stream) {
   if (!x) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(x->mu);
-  x->last_msg.clear();
-  if (x->T == 0 || nq == 0) return S3IMPH_OK;  // no tier data: nothing is written
-  if (!d_qpos || !d_out || !d_mask) return S3IMPH_ERR_INVALID;
-  try {
-    HIPCHECK(hipSetDevice(x->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+  return index_entry(x, [&](std::string& msg) -> int {
+    if (x->T == 0 || nq == 0) return S3IMPH_OK;  // no tier data: nothing is written
+    if (!d_qpos || !d_out || !d_mask) return S3IMPH_ERR_INVALID;
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
     const uint32_t qb = kQT / x->T;
     const uint64_t blocks = (nq + qb - 1) / qb;
     if (blocks > 0x7fffffffull) {
-      x->last_msg = "tier breakdown: more than 2^31 workgroups of queries in one batch";
+      msg = "tier breakdown: more than 2^31 workgroups of queries in one batch";
       return S3IMPH_ERR_INVALID;
     }
     k_index_tiers<<<(unsigned)blocks, kQT, 0, s>>>(x->tier_table, x->a.n, x->T, qb, d_qpos, nq, d_out, d_mask);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     return S3IMPH_OK;
-  } catch (const Fail& f) {
-    x->last_msg = f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_index_descendants_plan(s3imph_index* x, const uint64_t* d_qpos, const int32_t* d_rel, uint64_t nq, int mode,
@@ -1174,145 +1165,116 @@ int s3imph_index_descendants_plan(s3imph_index* x, const uint64_t* d_qpos, const
   if (!x || !n_rows || !total) return S3IMPH_ERR_INVALID;
   *n_rows = 0;
   *total = 0;
-  std::lock_guard<std::mutex> lk(x->mu);
-  x->last_msg.clear();
-  const bool filtered = min_count || min_bytes;
-  if ((mode != S3IMPH_DESC_AT && mode != S3IMPH_DESC_UPTO) || (mode == S3IMPH_DESC_UPTO && filtered) ||
-      (nq && (!d_qpos || !d_levels || !d_row_ptr)) || (nq && mode == S3IMPH_DESC_AT && !d_rel)) {
-    x->last_msg = mode == S3IMPH_DESC_UPTO && filtered ? "descendants plan: no filter with DescendantsUpToDepth"
-                                                       : "descendants plan: invalid argument";
-    return S3IMPH_ERR_INVALID;
-  }
-  if (filtered && !x->a.ocnt) {
-    x->last_msg = "descendants plan: the index has no object_count / total_bytes to filter on";
-    return S3IMPH_ERR_STATE;
-  }
-  try {
-    HIPCHECK(hipSetDevice(x->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
-    std::string msg;
-    const int rc = retry_on_nomem(x->ctx, s, &msg, [&] {
+  return index_entry(x, [&](std::string& msg) -> int {
+    const bool filtered = min_count || min_bytes;
+    if ((mode != S3IMPH_DESC_AT && mode != S3IMPH_DESC_UPTO) || (mode == S3IMPH_DESC_UPTO && filtered) ||
+        (nq && (!d_qpos || !d_levels || !d_row_ptr)) || (nq && mode == S3IMPH_DESC_AT && !d_rel)) {
+      msg = mode == S3IMPH_DESC_UPTO && filtered ? "descendants plan: no filter with DescendantsUpToDepth"
+                                                 : "descendants plan: invalid argument";
+      return S3IMPH_ERR_INVALID;
+    }
+    if (filtered && !x->a.ocnt) {
+      msg = "descendants plan: the index has no object_count / total_bytes to filter on";
+      return S3IMPH_ERR_STATE;
+    }
+    x->have_plan = false;  // whatever is thrown from here on leaves no plan (plan_locked sets it)
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
+    return retry_on_nomem(x->ctx, s, &msg, [&] {
       return plan_locked(x, d_qpos, d_rel, nq, mode, max_rel, min_count, min_bytes, d_levels, d_row_ptr, row_ptr_cap,
-                         n_rows, total, s);
+                         n_rows, total, s, &msg);
     });
-    if (rc != S3IMPH_OK && x->last_msg.empty()) x->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    x->have_plan = false;
-    x->last_msg = f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_index_descendants_fill(s3imph_index* x, uint64_t* d_out, uint64_t cap, void* stream) {
   if (!x) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(x->mu);
-  x->last_msg.clear();
-  if (!x->have_plan) {
-    x->last_msg = "descendants fill: no plan";
-    return S3IMPH_ERR_STATE;
-  }
-  if (cap < x->plan_total || (x->plan_total && !d_out)) {
-    x->last_msg = "descendants fill: out needs " + std::to_string(x->plan_total) + " entries";
-    return S3IMPH_ERR_INVALID;
-  }
-  if (x->plan_total == 0) return S3IMPH_OK;
-  try {
-    HIPCHECK(hipSetDevice(x->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
-    const int rc = fill_locked(x, d_out, "descendants fill", s);
+  return index_entry(x, [&](std::string& msg) -> int {
+    if (!x->have_plan) {
+      msg = "descendants fill: no plan";
+      return S3IMPH_ERR_STATE;
+    }
+    if (cap < x->plan_total || (x->plan_total && !d_out)) {
+      msg = "descendants fill: out needs " + std::to_string(x->plan_total) + " entries";
+      return S3IMPH_ERR_INVALID;
+    }
+    if (x->plan_total == 0) return S3IMPH_OK;
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
+    const int rc = fill_locked(x, d_out, "descendants fill", s, &msg);
     if (rc != S3IMPH_OK) return rc;
     HIPCHECK(hipStreamSynchronize(s));
     return S3IMPH_OK;
-  } catch (const Fail& f) {
-    x->last_msg = f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_index_cost_device(s3imph_index* x, const uint64_t* d_qpos, uint64_t nq, const s3imph_price_table* pt,
                              s3imph_cost* d_out, void* stream) {
   if (!x || !pt || (nq && (!d_qpos || !d_out))) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(x->mu);
-  x->last_msg.clear();
-  if (*price_table_fault(*pt)) {
-    x->last_msg = std::string("pricing: ") + price_table_fault(*pt);
-    return S3IMPH_ERR_INVALID;
-  }
-  if (nq == 0) return S3IMPH_OK;
-  try {
-    HIPCHECK(hipSetDevice(x->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+  return index_entry(x, [&](std::string& msg) -> int {
+    if (*price_table_fault(*pt)) {
+      msg = std::string("pricing: ") + price_table_fault(*pt);
+      return S3IMPH_ERR_INVALID;
+    }
+    if (nq == 0) return S3IMPH_OK;
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
     const uint32_t Tl = x->T ? x->T : 1, qb = kQT / Tl;
     const uint64_t blocks = (nq + qb - 1) / qb;
     if (blocks > 0x7fffffffull) {
-      x->last_msg = "pricing: more than 2^31 workgroups of queries in one batch";
+      msg = "pricing: more than 2^31 workgroups of queries in one batch";
       return S3IMPH_ERR_INVALID;
     }
     TierSlots slots{};
     std::memcpy(slots.id, x->tier_ids, sizeof slots.id);
-    k_index_cost<<<(unsigned)blocks, kQT, qb * sizeof(s3imph_cost), s>>>(x->tier_table, x->a.n, x->T, Tl, qb, slots, *pt, d_qpos, nq,
-                                                  reinterpret_cast<uint64_t*>(d_out));
+    k_index_cost<<<(unsigned)blocks, kQT, qb * sizeof(s3imph_cost), s>>>(
+        x->tier_table, x->a.n, x->T, Tl, qb, slots, *pt, d_qpos, nq, reinterpret_cast<uint64_t*>(d_out));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(s));
     return S3IMPH_OK;
-  } catch (const Fail& f) {
-    x->last_msg = f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_index_descendants_top(s3imph_index* x, int key, const s3imph_price_table* pt, uint32_t k,
                                  uint64_t* d_top_pos, uint64_t* d_top_key, uint32_t* d_top_n, void* stream) {
   if (!x) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(x->mu);
-  x->last_msg.clear();
-  const bool cost = key == S3IMPH_RANK_MONTHLY_COST;
-  if (k == 0 || (key != S3IMPH_RANK_OBJECT_COUNT && key != S3IMPH_RANK_TOTAL_BYTES && !cost) || (cost && !pt)) {
-    x->last_msg = "descendants top: invalid argument";
-    return S3IMPH_ERR_INVALID;
-  }
-  if (cost && *price_table_fault(*pt)) {
-    x->last_msg = std::string("pricing: ") + price_table_fault(*pt);
-    return S3IMPH_ERR_INVALID;
-  }
-  if (!x->have_plan) {
-    x->last_msg = "descendants top: no plan";
-    return S3IMPH_ERR_STATE;
-  }
-  if (!cost && !x->a.ocnt) {
-    x->last_msg = "descendants top: the index has no object_count / total_bytes to rank by";
-    return S3IMPH_ERR_STATE;
-  }
-  if (cost && x->T == 0) {
-    x->last_msg = "descendants top: the index has no tier data to price";
-    return S3IMPH_ERR_STATE;
-  }
-  if (x->plan_rows * k >= (1ull << 31)) {
-    x->last_msg = "descendants top: n_rows * k is 2^31 or more";
-    return S3IMPH_ERR_INVALID;
-  }
-  if (x->plan_total >= (1ull << 32)) {
-    x->last_msg = "descendants top: 2^32 positions or more in the plan";
-    return S3IMPH_ERR_INVALID;
-  }
-  if (x->plan_rows && (!d_top_pos || !d_top_key || !d_top_n)) {
-    x->last_msg = "descendants top: invalid argument";
-    return S3IMPH_ERR_INVALID;
-  }
-  try {
-    HIPCHECK(hipSetDevice(x->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : x->ctx->own_stream;
+  return index_entry(x, [&](std::string& msg) -> int {
+    const bool cost = key == S3IMPH_RANK_MONTHLY_COST;
+    if (k == 0 || (key != S3IMPH_RANK_OBJECT_COUNT && key != S3IMPH_RANK_TOTAL_BYTES && !cost) || (cost && !pt)) {
+      msg = "descendants top: invalid argument";
+      return S3IMPH_ERR_INVALID;
+    }
+    if (cost && *price_table_fault(*pt)) {
+      msg = std::string("pricing: ") + price_table_fault(*pt);
+      return S3IMPH_ERR_INVALID;
+    }
+    if (!x->have_plan) {
+      msg = "descendants top: no plan";
+      return S3IMPH_ERR_STATE;
+    }
+    if (!cost && !x->a.ocnt) {
+      msg = "descendants top: the index has no object_count / total_bytes to rank by";
+      return S3IMPH_ERR_STATE;
+    }
+    if (cost && x->T == 0) {
+      msg = "descendants top: the index has no tier data to price";
+      return S3IMPH_ERR_STATE;
+    }
+    if (x->plan_rows * k >= (1ull << 31)) {
+      msg = "descendants top: n_rows * k is 2^31 or more";
+      return S3IMPH_ERR_INVALID;
+    }
+    if (x->plan_total >= (1ull << 32)) {
+      msg = "descendants top: 2^32 positions or more in the plan";
+      return S3IMPH_ERR_INVALID;
+    }
+    if (x->plan_rows && (!d_top_pos || !d_top_key || !d_top_n)) {
+      msg = "descendants top: invalid argument";
+      return S3IMPH_ERR_INVALID;
+    }
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
     const s3imph_price_table none{};
-    std::string msg;
-    const int rc = retry_on_nomem(x->ctx, s, &msg,
-                                  [&] { return top_locked(x, key, cost ? *pt : none, k, d_top_pos, d_top_key, d_top_n, s); });
-    if (rc != S3IMPH_OK && x->last_msg.empty()) x->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    x->last_msg = f.msg;
-    return f.code;
-  }
+    return retry_on_nomem(x->ctx, s, &msg, [&] {
+      return top_locked(x, key, cost ? *pt : none, k, d_top_pos, d_top_key, d_top_n, s, &msg);
+    });
+  });
 }
 
 }  // extern "C"

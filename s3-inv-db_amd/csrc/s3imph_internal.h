@@ -512,6 +512,7 @@ int feed_build(Feed* f, std::vector<uint8_t>* mph, const std::function<FeedSink*
 
 // ---- host helpers (s3imph_host.cpp) -------------------------------------------
 void set_err(char* err, size_t errlen, const std::string& msg);
+bool is_dir(const std::string& p);
 void s3id_header(uint8_t out[kS3idHeaderSize], uint64_t count, uint32_t width);  // format.go:25-32
 // a file made of `count` pieces, piece(i, &p, &n, &off) giving bytes p[0..n) at file offset
 // off; the pieces are pwrite()-n by up to 8 threads

@@ -20,12 +20,9 @@
 // (k_merge_heads); one scan numbers the heads, one sums their byte lengths; an output row sums its
 // members, which are contiguous in the merged order (k_merge_rows); the bytes are copied by output
 // word from the head's place in the input blob (emit_word, s3imph_keys.h).
-#include <sys/stat.h>
-
-#include <cstdlib>
 #include <cstring>
 
-#include "s3imph_ctx.h"
+#include "s3imph_entry.h"
 #include "s3imph_keys.h"
 #include "s3imph_prim.h"
 #include "s3imph_tiers.h"
@@ -543,21 +540,12 @@ void download_rows(s3imph_ctx* c, const DevRows& r, bool tiers, HostRun* h) {
   h->depth.resize(r.n);
   h->count.resize(r.n);
   h->bytes.resize(r.n);
-  if (r.blob_bytes) HIPCHECK(hipMemcpy(h->blob.data(), r.blob, r.blob_bytes, hipMemcpyDeviceToHost));
-  staged_copy(c, false, h->offsets.data(), r.offsets, (r.n + 1) * 8);
-  if (r.n) {
-    staged_copy(c, false, h->depth.data(), r.depth, r.n * 4);
-    staged_copy(c, false, h->count.data(), r.ocnt, r.n * 8);
-    staged_copy(c, false, h->bytes.data(), r.tbytes, r.n * 8);
-  }
   if (tiers) {
     h->tcount.resize(kNT * r.n);
     h->tbytes.resize(kNT * r.n);
-    if (r.n) {
-      staged_copy(c, false, h->tcount.data(), r.tier_count, kNT * r.n * 8);
-      staged_copy(c, false, h->tbytes.data(), r.tier_bytes, kNT * r.n * 8);
-    }
   }
+  rows_to_host(c, r, tiers, h->blob.data(), h->offsets.data(), h->depth.data(), h->count.data(), h->bytes.data(),
+               h->tcount.data(), h->tbytes.data());
 }
 
 // At most kMaxRuns host runs concatenated on upload (offsets rebased onto one blob), merged, the
@@ -683,18 +671,6 @@ int merge_runs(s3imph_ctx* c, DevGuard& g, const s3imph_row_run* runs, uint64_t 
   return rc;
 }
 
-bool is_dir(const std::string& p) {
-  struct stat st;
-  return ::stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
-}
-
-template <typename T>
-T* host_array(uint64_t count) {
-  T* p = static_cast<T*>(std::malloc(std::max<uint64_t>(count, 1) * sizeof(T)));
-  if (!p) throw std::bad_alloc();
-  return p;
-}
-
 // s3imph_index_from_rows_host: the merge, then the back half of the listing builds.
 int index_from_rows(int device, const s3imph_row_run* runs, uint64_t k, const char* out_dir, char* err,
                     size_t errlen) {
@@ -711,43 +687,21 @@ int index_from_rows(int device, const s3imph_row_run* runs, uint64_t k, const ch
     set_err(err, errlen, "create mph file: open " + dir + "/mph.bin: no such directory");
     return S3IMPH_ERR_IO;
   }
-  std::string msg;
-  try {
-    IndexHostArrays h;
-    if (rows) {
-      s3imph_ctx* c = default_ctx(device, &msg);
-      if (!c) {
-        set_err(err, errlen, "merge: " + msg);
-        return S3IMPH_ERR_HIP;
-      }
-      std::lock_guard<std::mutex> lk(c->mu);
-      HIPCHECK(hipSetDevice(c->device));
-      hipStream_t s = c->own_stream;
-      // one device residency: the rows stay in HBM from the merge to the last array
-      const int rc = retry_on_nomem(c, s, &msg, [&]() -> int {
-        DevGuard g;
-        DevRows r;
-        s3imph_merge_info mi;
-        const int rc2 = merge_runs(c, g, runs, k, tiers, &r, &mi, &msg);
-        if (rc2 != S3IMPH_OK) return rc2;
-        h.n = r.n;
-        return index_arrays_from_rows(c, g, r, tiers, h, s, &msg);
-      });
-      if (rc != S3IMPH_OK) {
-        set_err(err, errlen, msg);
-        return rc;
-      }
-    }
-    const int rc = write_index_dir(dir, h, tiers, &msg);
-    if (rc != S3IMPH_OK) set_err(err, errlen, msg);
-    return rc;
-  } catch (const Fail& f) {
-    set_err(err, errlen, "merge: " + f.msg);
-    return f.code;
-  } catch (const std::bad_alloc&) {
-    set_err(err, errlen, "merge: out of host memory");
-    return S3IMPH_ERR_NOMEM;
+  IndexHostArrays h;
+  if (rows) {
+    // one device residency: the rows stay in HBM from the merge to the last array
+    const int rc = host_entry(device, "merge: ", err, errlen, [&](s3imph_ctx* c, hipStream_t s, std::string& msg) {
+      DevGuard g;
+      DevRows r;
+      s3imph_merge_info mi;
+      const int rc2 = merge_runs(c, g, runs, k, tiers, &r, &mi, &msg);
+      if (rc2 != S3IMPH_OK) return rc2;
+      h.n = r.n;
+      return index_arrays_from_rows(c, g, r, tiers, h, s, &msg);
+    });
+    if (rc != S3IMPH_OK) return rc;
   }
+  return host_call("merge: ", err, errlen, [&](std::string& msg) { return write_index_dir(dir, h, tiers, &msg); });
 }
 
 }  // namespace
@@ -776,39 +730,20 @@ int rowset_add_chunk(s3imph_rowset* rs, const uint8_t* keys, const uint64_t* kof
   for (uint64_t i = 0; csv && i < csv->n_files; ++i) csv_bytes += csv->len[i];
   if (!m && !csv_bytes) return S3IMPH_OK;  // a chunk without an object adds no run
   if (csv) tiers = rs->tiers ? &kWanted : nullptr;
-  std::string msg;
-  try {
-    s3imph_ctx* c = default_ctx(rs->device, &msg);
-    if (!c) {
-      set_err(err, errlen, (csv ? "csv: " : "aggregate: ") + msg);
-      return S3IMPH_ERR_HIP;
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHECK(hipSetDevice(c->device));
-    HostRun run;
-    const int rc = retry_on_nomem(c, c->own_stream, &msg, [&]() -> int {
-      DevGuard g;
-      DevRows r;
-      const int rc2 = rows_from_host(c, g, keys, koff, sizes, m, rs->max_depth, &r, &msg, tiers, true, csv);
-      if (rc2 != S3IMPH_OK) return rc2;
-      run = HostRun();
-      if (r.m && r.n) download_rows(c, r, rs->tiers, &run);
-      return S3IMPH_OK;
-    });
-    if (rc != S3IMPH_OK) {
-      set_err(err, errlen, msg);
-      return rc;
-    }
-    if (run.n) rs->runs.push_back(std::move(run));
-    return S3IMPH_OK;
-  } catch (const Fail& f) {
-    set_err(err, errlen,
-            f.msg.compare(0, 6, "sort: ") == 0 || f.msg.compare(0, 5, "csv: ") == 0 ? f.msg : "aggregate: " + f.msg);
-    return f.code;
-  } catch (const std::bad_alloc&) {
-    set_err(err, errlen, "aggregate: out of host memory");
-    return S3IMPH_ERR_NOMEM;
-  }
+  return host_entry(
+      rs->device, "aggregate: ", err, errlen,
+      [&](s3imph_ctx* c, hipStream_t, std::string& msg) {
+        DevGuard g;
+        DevRows r;
+        const int rc2 = rows_from_host(c, g, keys, koff, sizes, m, rs->max_depth, &r, &msg, tiers, true, csv);
+        if (rc2 == S3IMPH_OK && r.m && r.n) {  // the last step: a retry finds no run of this chunk
+          HostRun run;
+          download_rows(c, r, rs->tiers, &run);
+          rs->runs.push_back(std::move(run));
+        }
+        return rc2;
+      },
+      csv ? "csv: " : nullptr);
 }
 
 }  // namespace
@@ -824,49 +759,35 @@ int s3imph_merge_rows_plan_device(s3imph_ctx* c, const uint8_t* d_blob, const ui
                                   const uint64_t* d_tier_count, const uint64_t* d_tier_bytes, uint64_t tier_stride,
                                   const uint64_t* run_starts, uint32_t k, s3imph_merge_info* info, void* stream) {
   if (!c || !info) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg = merge_args_bad(d_blob, d_offsets, d_depth, d_count, d_bytes, d_tier_count, d_tier_bytes,
-                                   tier_stride, run_starts, k);
-  if (!msg.empty()) {  // before any device work
-    std::memset(info, 0, sizeof *info);
-    info->first_unsorted = UINT64_MAX;
-    info->n_runs = k;
-    if (c->mrg) c->mrg->have_plan = false;
-    c->last_msg = msg;
-    return S3IMPH_ERR_INVALID;
-  }
-  try {
-    if (run_starts && run_starts[k]) HIPCHECK(hipSetDevice(c->device));  // no row: no device work
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = retry_on_nomem(c, s, &msg, [&] {
+  return device_entry(c, "merge: ", [&](std::string& msg) -> int {
+    msg = merge_args_bad(d_blob, d_offsets, d_depth, d_count, d_bytes, d_tier_count, d_tier_bytes, tier_stride,
+                         run_starts, k);
+    if (!msg.empty()) {  // before any device work
+      std::memset(info, 0, sizeof *info);
+      info->first_unsorted = UINT64_MAX;
+      info->n_runs = k;
+      if (c->mrg) c->mrg->have_plan = false;
+      return S3IMPH_ERR_INVALID;
+    }
+    const bool rows = run_starts && run_starts[k];  // no row: no device work
+    hipStream_t s = rows ? use_device(c->device, stream, c->own_stream) : nullptr;
+    return retry_on_nomem(c, s, &msg, [&] {
       return merge_plan(c, d_blob, d_offsets, d_depth, d_count, d_bytes, d_tier_count, d_tier_bytes, tier_stride,
                         run_starts, k, info, s, &msg);
     });
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = "merge: " + f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_merge_rows_fill_device(s3imph_ctx* c, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offsets,
                                   uint32_t* d_depth, uint64_t* d_count, uint64_t* d_bytes, uint64_t* d_tier_count,
                                   uint64_t* d_tier_bytes, uint64_t n_cap, void* stream) {
   if (!c) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    if (c->mrg && c->mrg->have_plan) HIPCHECK(hipSetDevice(c->device));  // without a plan: no device work
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = merge_fill(c, d_blob, blob_cap, d_offsets, d_depth, d_count, d_bytes, d_tier_count, d_tier_bytes,
-                              n_cap, s, &msg);
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = "merge: " + f.msg;
-    return f.code;
-  }
+  return device_entry(c, "merge: ", [&](std::string& msg) {
+    const bool plan = c->mrg && c->mrg->have_plan;  // without a plan: no device work
+    hipStream_t s = plan ? use_device(c->device, stream, c->own_stream) : nullptr;
+    return merge_fill(c, d_blob, blob_cap, d_offsets, d_depth, d_count, d_bytes, d_tier_count, d_tier_bytes, n_cap, s,
+                      &msg);
+  });
 }
 
 int s3imph_merge_rows_host(int device, const s3imph_row_run* runs, uint64_t k, uint8_t** blob, uint64_t** offsets,
@@ -882,93 +803,23 @@ int s3imph_merge_rows_host(int device, const s3imph_row_run* runs, uint64_t k, u
     return S3IMPH_ERR_INVALID;
   }
   if (tiers && (!tier_count || !tier_bytes || !present_mask)) return S3IMPH_ERR_INVALID;
-  uint64_t *no_count = nullptr, *no_bytes = nullptr, no_mask = 0;
   s3imph_merge_info no_info;
-  if (!tier_count) tier_count = &no_count;
-  if (!tier_bytes) tier_bytes = &no_bytes;
-  if (!present_mask) present_mask = &no_mask;
   if (!info) info = &no_info;
-  auto drop = [&] {
-    std::free(*blob);
-    std::free(*offsets);
-    std::free(*depth);
-    std::free(*object_count);
-    std::free(*total_bytes);
-    std::free(*tier_count);
-    std::free(*tier_bytes);
-    *blob = nullptr;
-    *offsets = nullptr;
-    *depth = nullptr;
-    *object_count = *total_bytes = nullptr;
-    *tier_count = *tier_bytes = nullptr;
-  };
-  *blob = nullptr;
-  *offsets = nullptr;
-  *depth = nullptr;
-  *object_count = *total_bytes = nullptr;
-  *tier_count = *tier_bytes = nullptr;
-  *present_mask = 0;
-  *n = 0;
+  HostRows out(blob, offsets, depth, object_count, total_bytes, tier_count, tier_bytes, present_mask, n);
+  out.reset();
   std::memset(info, 0, sizeof *info);
   info->first_unsorted = UINT64_MAX;
   info->n_runs = (uint32_t)std::min<uint64_t>(k, UINT32_MAX);
-  std::string msg;
-  try {
-    if (rows == 0) {
-      *offsets = host_array<uint64_t>(1);
-      (*offsets)[0] = 0;
-      return S3IMPH_OK;
-    }
-    s3imph_ctx* c = default_ctx(device, &msg);
-    if (!c) {
-      set_err(err, errlen, "merge: " + msg);
-      return S3IMPH_ERR_HIP;
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHECK(hipSetDevice(c->device));
-    const int rc = retry_on_nomem(c, c->own_stream, &msg, [&]() -> int {
-      DevGuard g;
-      DevRows r;
-      const int rc2 = merge_runs(c, g, runs, k, tiers, &r, info, &msg);
-      if (rc2 != S3IMPH_OK) return rc2;
-      drop();
-      *blob = host_array<uint8_t>(r.blob_bytes);
-      *offsets = host_array<uint64_t>(r.n + 1);
-      *depth = host_array<uint32_t>(r.n);
-      *object_count = host_array<uint64_t>(r.n);
-      *total_bytes = host_array<uint64_t>(r.n);
-      if (r.blob_bytes) HIPCHECK(hipMemcpy(*blob, r.blob, r.blob_bytes, hipMemcpyDeviceToHost));
-      staged_copy(c, false, *offsets, r.offsets, (r.n + 1) * 8);
-      staged_copy(c, false, *depth, r.depth, r.n * 4);
-      staged_copy(c, false, *object_count, r.ocnt, r.n * 8);
-      staged_copy(c, false, *total_bytes, r.tbytes, r.n * 8);
-      if (tiers) {
-        *tier_count = host_array<uint64_t>(kNT * r.n);
-        *tier_bytes = host_array<uint64_t>(kNT * r.n);
-        staged_copy(c, false, *tier_count, r.tier_count, kNT * r.n * 8);
-        staged_copy(c, false, *tier_bytes, r.tier_bytes, kNT * r.n * 8);
-        *present_mask = r.present_mask;
-      }
-      *n = r.n;
-      return (int)S3IMPH_OK;
-    });
-    if (rc != S3IMPH_OK) {
-      drop();
-      *n = 0;
-      set_err(err, errlen, msg);
-    }
-    return rc;
-  } catch (const Fail& f) {
-    drop();
-    *n = 0;
-    set_err(err, errlen, "merge: " + f.msg);
-    return f.code;
-  } catch (const std::bad_alloc&) {
-    drop();
-    *n = 0;
-    set_err(err, errlen, "merge: out of host memory");
-    return S3IMPH_ERR_NOMEM;
-  }
+  if (rows == 0) return host_call("merge: ", err, errlen, [&](std::string&) { return out.none(); });
+  const int rc = host_entry(device, "merge: ", err, errlen, [&](s3imph_ctx* c, hipStream_t, std::string& msg) {
+    DevGuard g;
+    DevRows r;
+    const int rc2 = merge_runs(c, g, runs, k, tiers, &r, info, &msg);
+    if (rc2 == S3IMPH_OK) out.download(c, r, tiers);
+    return rc2;
+  });
+  if (rc != S3IMPH_OK) out.drop();
+  return rc;
 }
 
 int s3imph_index_from_rows_host(int device, const s3imph_row_run* runs, uint64_t k, const char* out_dir, char* err,

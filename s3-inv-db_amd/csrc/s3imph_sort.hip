@@ -34,7 +34,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "s3imph_ctx.h"
+#include "s3imph_entry.h"
 #include "s3imph_keys.h"
 #include "s3imph_prim.h"
 
@@ -436,20 +436,12 @@ extern "C" {
 int s3imph_sort_objects_device(s3imph_ctx* c, const uint8_t* d_keys, const uint64_t* d_key_offsets, uint64_t m,
                                uint32_t* d_order, s3imph_sort_info* info, void* stream) {
   if (!c || !info || (m >> 32) || (m && (!d_keys || !d_key_offsets || !d_order))) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = retry_on_nomem(c, s, &msg, [&] {
+  return device_entry(c, "sort: ", [&](std::string& msg) {
+    hipStream_t s = use_device(c->device, stream, c->own_stream);
+    return retry_on_nomem(c, s, &msg, [&] {
       return sort_objects(c, d_keys, d_key_offsets, m, d_order, info, s, &msg);
     });
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = "sort: " + f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_gather_objects_device(s3imph_ctx* c, const uint8_t* d_keys, const uint64_t* d_key_offsets,
@@ -458,21 +450,13 @@ int s3imph_gather_objects_device(s3imph_ctx* c, const uint8_t* d_keys, const uin
                                  uint64_t* d_sizes_out, uint8_t* d_tiers_out, void* stream) {
   if (!c || !d_offsets_out || (m >> 32) || (m && (!d_keys || !d_key_offsets || !d_order))) return S3IMPH_ERR_INVALID;
   if (!d_sizes != !d_sizes_out || !d_tiers != !d_tiers_out) return S3IMPH_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(c->mu);
-  std::string msg;
-  try {
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->own_stream;
-    const int rc = retry_on_nomem(c, s, &msg, [&] {
+  return device_entry(c, "sort: ", [&](std::string& msg) {
+    hipStream_t s = use_device(c->device, stream, c->own_stream);
+    return retry_on_nomem(c, s, &msg, [&] {
       return gather_objects(c, d_keys, d_key_offsets, d_sizes, d_tiers, m, d_order, d_keys_out, keys_cap,
                             d_offsets_out, d_sizes_out, d_tiers_out, s, &msg);
     });
-    c->last_msg = msg;
-    return rc;
-  } catch (const Fail& f) {
-    c->last_msg = "sort: " + f.msg;
-    return f.code;
-  }
+  });
 }
 
 int s3imph_sort_objects_host(int device, const uint8_t* keys, const uint64_t* key_offsets, uint64_t m,
@@ -482,46 +466,27 @@ int s3imph_sort_objects_host(int device, const uint8_t* keys, const uint64_t* ke
   std::memset(info, 0, sizeof *info);
   info->first_unsorted = UINT64_MAX;
   if (m == 0) return S3IMPH_OK;
-  std::string msg;
   uint32_t* out = static_cast<uint32_t*>(std::malloc(m * sizeof(uint32_t)));
   if (!out) {
     set_err(err, errlen, "sort: out of host memory");
     return S3IMPH_ERR_NOMEM;
   }
-  try {
-    s3imph_ctx* c = default_ctx(device, &msg);
-    if (!c) {
-      std::free(out);
-      set_err(err, errlen, "sort: " + msg);
-      return S3IMPH_ERR_HIP;
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHECK(hipSetDevice(c->device));
-    hipStream_t s = c->own_stream;
-    const int rc = retry_on_nomem(c, s, &msg, [&]() -> int {
-      DevGuard g;
-      uint8_t* d_keys = nullptr;
-      uint64_t* d_koff = nullptr;
-      uint32_t* d_order = nullptr;
-      upload_keys(c, g, keys, key_offsets, m, d_keys, d_koff);
-      g.make(d_order, m);
-      const int rc2 = sort_objects(c, d_keys, d_koff, m, d_order, info, s, &msg);
-      if (rc2 != S3IMPH_OK) return rc2;
-      staged_copy(c, false, out, d_order, m * 4);
-      return S3IMPH_OK;
-    });
-    if (rc != S3IMPH_OK) {
-      std::free(out);
-      set_err(err, errlen, msg);
-      return rc;
-    }
+  const int rc = host_entry(device, "sort: ", err, errlen, [&](s3imph_ctx* c, hipStream_t s, std::string& msg) {
+    DevGuard g;
+    uint8_t* d_keys = nullptr;
+    uint64_t* d_koff = nullptr;
+    uint32_t* d_order = nullptr;
+    upload_keys(c, g, keys, key_offsets, m, d_keys, d_koff);
+    g.make(d_order, m);
+    const int rc2 = sort_objects(c, d_keys, d_koff, m, d_order, info, s, &msg);
+    if (rc2 == S3IMPH_OK) staged_copy(c, false, out, d_order, m * 4);
+    return rc2;
+  });
+  if (rc == S3IMPH_OK)
     *order = out;
-    return S3IMPH_OK;
-  } catch (const Fail& f) {
+  else
     std::free(out);
-    set_err(err, errlen, "sort: " + f.msg);
-    return f.code;
-  }
+  return rc;
 }
 
 int s3imph_index_from_unsorted_objects_host(int device, const uint8_t* keys, const uint64_t* key_offsets,
