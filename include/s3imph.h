@@ -446,6 +446,63 @@ int s3imph_index_descendants_plan(s3imph_index *idx, const uint64_t *d_qpos, con
                                   uint64_t row_ptr_cap, uint64_t *n_rows, uint64_t *total, void *stream);
 int s3imph_index_descendants_fill(s3imph_index *idx, uint64_t *d_out, uint64_t cap, void *stream);
 
+/* The stored prefixes in HBM — what OpenMPHF loads "for reverse lookup" (mphf.go:226-238;
+ * OpenBlob, reader.go:213-229) — and the three queries over them: PrefixString (index.go:179;
+ * BlobReader.Get, reader.go:250-270), MPHF.LookupWithVerify (mphf.go:306-320) and VerifyMPHF
+ * (mphf.go:372-393).  Every one of them returns S3IMPH_ERR_STATE, "prefix blob not loaded"
+ * (mphf.go:374), on a handle without prefixes.
+ *
+ * s3imph_index_open_flags: flags == 0 is s3imph_index_open.  With S3IMPH_OPEN_PREFIXES a missing
+ * prefix_blob.bin opens the handle without prefixes (no error, as in OpenMPHF); a present one needs
+ * prefix_offsets.u64: error texts "open MPHF: open prefix blob: open offsets: ...", a missing
+ * file S3IMPH_ERR_IO, a bad S3ID header or a width other than 8 S3IMPH_ERR_FORMAT.  What the
+ * reference checks per Get is checked once here, on the host before the device is selected:
+ * S3IMPH_ERR_FORMAT unless the offsets hold Count() + 1 entries, never decrease and end at or
+ * before the blob's size (offsets[0] != 0 and slack after the last offset are allowed).  The blob
+ * goes to HBM zero-padded to round_up(size, 8) + 8 bytes, the offsets as they are.  An unknown
+ * flag is S3IMPH_ERR_INVALID. */
+#define S3IMPH_OPEN_PREFIXES 1
+int s3imph_index_open_flags(int device, const char *dir, unsigned flags, s3imph_index **out, char *err,
+                            size_t errlen);
+/* The same for a handle of s3imph_index_attach: Count() + 1 offsets and the blob they index, in
+ * HBM, borrowed (they must outlive the handle) and taken on trust like the other attached arrays;
+ * d_blob readable up to round_up(offsets[Count()], 8).  Null pointers are S3IMPH_ERR_INVALID; a
+ * second attach replaces the first (and drops a prefixes plan). */
+int s3imph_index_attach_prefixes(s3imph_index *idx, const uint8_t *d_blob, const uint64_t *d_offsets);
+/* 1 when the handle holds the prefix blob, else 0. */
+int s3imph_index_has_prefixes(const s3imph_index *idx);
+
+/* PrefixString — index.go:179 (MPHF.GetPrefix; BlobReader.Get, reader.go:250-270) — for nq
+ * positions, in two steps like the descendants: plan writes d_out_offsets (nq + 1 entries, the
+ * exclusive prefix of the lengths; *total = d_out_offsets[nq]) and, when given, d_found; fill
+ * writes the rows of the last plan back to back, row q at d_out[out_offsets[q] ..], so (d_out,
+ * d_out_offsets) is a key blob in the layout of s3imph_index_lookup_device.  pos >= Count() (the
+ * UINT64_MAX of a failed lookup included) is a 0-byte row with found = 0 — the reference's
+ * ErrBoundsCheck; "" (the root) is a 0-byte row with found = 1.
+ * fill writes whole 8-byte words: cap (bytes) must be >= round_up(total, 8), the bytes past total
+ * in the last word are zeros; d_out may have any alignment.  S3IMPH_ERR_INVALID when cap is too
+ * small or nq >= 2^31, S3IMPH_ERR_STATE without a plan.  The handle keeps what fill needs (d_qpos
+ * may be freed after plan); a later prefixes plan replaces the earlier one; a prefixes plan and a
+ * descendants plan do not disturb each other.  nq == 0 is OK with *total = 0. */
+int s3imph_index_prefixes_plan(s3imph_index *idx, const uint64_t *d_qpos, uint64_t nq,
+                               uint64_t *d_out_offsets /* nq + 1 */, uint32_t *d_found /* nq, nullable */,
+                               uint64_t *total, void *stream);
+int s3imph_index_prefixes_fill(s3imph_index *idx, uint8_t *d_out, uint64_t cap, void *stream);
+
+/* MPHF.LookupWithVerify — mphf.go:306-320: s3imph_index_lookup_device's contract, and a position
+ * survives only if the stored prefix there has the query's length and bytes (mphf.go:312-317);
+ * otherwise UINT64_MAX.  The one lookup that cannot return a false positive. */
+int s3imph_index_lookup_verify_device(s3imph_index *idx, const uint8_t *d_blob, const uint64_t *d_offsets,
+                                      uint64_t nq, uint64_t *d_pos_out, void *stream);
+
+/* VerifyMPHF — mphf.go:372-393: every stored prefix i is looked up; *n_bad = the number of i with
+ * Lookup(prefix i) != i, *first_bad the smallest of them and *first_got what the lookup gave there
+ * (UINT64_MAX: "lookup failed", mphf.go:384; else "lookup returned wrong pos", mphf.go:387); both
+ * are UINT64_MAX when n_bad == 0, the reference's nil.  S3IMPH_OK whenever it ran; 8 Count() bytes
+ * of HBM in the handle's workspace. */
+int s3imph_index_verify_device(s3imph_index *idx, uint64_t *n_bad, uint64_t *first_bad, uint64_t *first_got,
+                               void *stream);
+
 /* ------------------------------------------------------------------------
  * 5d. extsort.Aggregator + SortPrefixRows (pkg/extsort/aggregator.go:44-76, :138-) on the
  *     GPU: a byte-sorted object listing (keys in the blob / offsets layout, one size per key)

@@ -12,7 +12,10 @@
 //   over OpenTierStats / GetBreakdown[All] (tierstats.go:108-215; include/s3imph.h section 5e);
 //   query --estimate-cost: TierBreakdown(pos) -> pricing.ComputeMonthlyCost (internal/cli/cli.go:
 //   227-296, pkg/pricing/pricing.go:159-240; include/s3imph.h section 5h), and the plan's rows
-//   ranked by it (an extension: stable segmented sort of the filled rows, first k of each kept).
+//   ranked by it (an extension: stable segmented sort of the filled rows, first k of each kept);
+//   PrefixString   index.go:179 over the prefix blob OpenMPHF loads (mphf.go:226-238; OpenBlob and
+//   BlobReader.Get, reader.go:213-270), for a batch; MPHF.LookupWithVerify (mphf.go:306-320);
+//   VerifyMPHF (mphf.go:372-393).
 //
 // GPU formulation.  A batch of descendants queries is a CSR: `levels` per query, `row_ptr`
 // over the result rows, and the flat list of positions.  The plan step runs one lane per
@@ -442,6 +445,107 @@ __global__ __launch_bounds__(kChunkT) void k_desc_filter(IndexArrays a, const ui
   }
 }
 
+// ---- the prefix blob: PrefixString, LookupWithVerify, VerifyMPHF -----------------------------
+// The stored prefixes (prefix_blob.bin, prefix_offsets.u64) in HBM: n + 1 offsets that never
+// decrease, the blob readable up to end8 = round_up(offsets[n], 8).
+struct PrefixBlob {
+  const uint8_t* blob = nullptr;
+  const uint64_t* off = nullptr;
+  uint64_t end8 = 0;
+};
+
+// PrefixString's length pass (BlobReader.Get, reader.go:250-270), one lane per query: the row's
+// length, its source address in the blob (so the emit never goes back to offsets[pos]) and
+// found; pos >= Count() is a 0-byte row with found = 0.
+__global__ __launch_bounds__(kQT) void k_names_len(PrefixBlob pb, uint64_t n, const uint64_t* __restrict__ qpos,
+                                                   uint64_t nq, uint64_t* __restrict__ src,
+                                                   uint64_t* __restrict__ len, uint32_t* __restrict__ found) {
+  const uint64_t i = (uint64_t)blockIdx.x * kQT + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t p = qpos[i];
+  const bool ok = p < n;
+  uint64_t o0 = 0, o1 = 0;
+  if (ok) {
+    o0 = pb.off[p];
+    o1 = pb.off[p + 1];
+  }
+  src[i] = o0;
+  len[i] = o1 - o0;
+  if (found) found[i] = ok ? 1u : 0u;
+}
+
+// The emit's chunks: the row of each chunk's first output byte (chunk_owner), one lane per chunk.
+__global__ __launch_bounds__(kChunkT) void k_names_bounds(const uint64_t* __restrict__ U, uint64_t entries,
+                                                          uint64_t nchunks, uint64_t* __restrict__ out) {
+  const uint64_t t = (uint64_t)blockIdx.x * kChunkT + threadIdx.x;
+  if (t < nchunks) out[t] = chunk_owner(U, entries, 8ull * kChunkT, 0, t);
+}
+
+// The rows back to back, by 8-byte word of the output (emit_word): row r from blob address src[r].
+__global__ __launch_bounds__(kChunkT) void k_names_emit(PrefixBlob pb, const uint64_t* __restrict__ offsets,
+                                                        const uint64_t* __restrict__ bounds,
+                                                        const uint64_t* __restrict__ src, uint64_t n_rows,
+                                                        uint64_t total, uint8_t* __restrict__ out) {
+  emit_word<kChunkT>(pb.blob, pb.end8, offsets, bounds, n_rows, total, out, [&](uint64_t r) { return src[r]; });
+}
+
+// LookupWithVerify's second half (mphf.go:312-317), one lane per query: the position survives
+// only if the stored prefix there has the query's length and bytes; lengths first, then words
+// through load8 on both blobs (any alignment), the last word masked.
+__global__ __launch_bounds__(kQT) void k_lookup_verify(PrefixBlob pb, uint64_t n, const uint8_t* __restrict__ qblob,
+                                                       const uint64_t* __restrict__ qoff, uint64_t nq,
+                                                       uint64_t* __restrict__ res) {
+  const uint64_t i = (uint64_t)blockIdx.x * kQT + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t p = res[i];
+  if (p == ~0ull) return;
+  bool same = p < n;
+  if (same) {
+    const uint64_t q0 = qoff[i], len = qoff[i + 1] - q0;
+    const uint64_t s0 = pb.off[p];
+    same = pb.off[p + 1] - s0 == len;
+    if (same && len) {
+      const uint64_t qend8 = (qoff[nq] + 7) & ~7ull;
+      for (uint64_t k = 0; k < len; k += 8) {
+        uint64_t x = load8(qblob, q0 + k, qend8) ^ load8(pb.blob, s0 + k, pb.end8);
+        if (len - k < 8) x &= (1ull << (8 * (len - k))) - 1;
+        if (x) {
+          same = false;
+          break;
+        }
+      }
+    }
+  }
+  if (!same) res[i] = ~0ull;
+}
+
+// VerifyMPHF's reduction (mphf.go:372-393) over got[i] = Lookup(prefix i): r[0] += the i with
+// got[i] != i, r[1] = the smallest of them (r[1] starts at UINT64_MAX).  One atomic pair per wave
+// that saw one.
+__global__ __launch_bounds__(kQT) void k_verify_reduce(const uint64_t* __restrict__ got, uint64_t n,
+                                                       unsigned long long* __restrict__ r) {
+  unsigned long long bad = 0, first = ~0ull;
+  for (uint64_t i = (uint64_t)blockIdx.x * kQT + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kQT)
+    if (got[i] != i) {
+      ++bad;
+      first = first < i ? first : i;
+    }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    bad += __shfl_xor(bad, o);
+    const unsigned long long f = __shfl_xor(first, o);
+    first = first < f ? first : f;
+  }
+  if (lane_id() == 0 && bad) {
+    atomicAdd(&r[0], bad);
+    atomicMin(&r[1], first);
+  }
+}
+// r[2] = what the lookup gave at the first bad index.
+__global__ void k_verify_got(const uint64_t* __restrict__ got, unsigned long long* __restrict__ r) {
+  if (r[0]) r[2] = got[r[1]];
+}
+
 // ---- host side: files -------------------------------------------------------------------------
 struct HostArray {
   std::vector<uint64_t> store;  // 8-byte aligned payload
@@ -719,6 +823,52 @@ int load_host_index(const std::string& dir, HostIndex* h, std::string* msg) {
   return load_host_tiers(dir, n, h, msg);
 }
 
+// What OpenMPHF loads for reverse lookup (mphf.go:226-238; OpenBlob, reader.go:213-229), checked
+// on the host for an index of n nodes: no prefix_blob.bin is no prefixes, not an error.
+struct HostPrefixes {
+  bool present = false;
+  HostArray off;
+  std::vector<uint64_t> blob;  // round_up(size, 8) + 8 bytes, zero-padded (load8's contract)
+};
+
+int load_host_prefixes(const std::string& dir, uint64_t n, HostPrefixes* p, std::string* msg) {
+  const std::string bp = dir + "/prefix_blob.bin";
+  if (!file_exists(bp)) return S3IMPH_OK;
+  auto fail = [&](const std::string& m, int code) {
+    *msg = "open MPHF: open prefix blob: " + m;
+    return code;
+  };
+  FILE* f = std::fopen(bp.c_str(), "rb");
+  if (!f) return fail("open blob: open " + bp + ": " + std::strerror(errno), S3IMPH_ERR_IO);
+  struct Close {
+    FILE* f;
+    ~Close() { std::fclose(f); }
+  } closer{f};
+  struct stat st;
+  if (::fstat(fileno(f), &st) != 0) return fail("open blob: stat " + bp + ": " + std::strerror(errno), S3IMPH_ERR_IO);
+  const uint64_t size = (uint64_t)st.st_size;
+  std::string m;
+  const int rc = read_array(dir + "/prefix_offsets.u64", 8, &p->off, &m);
+  if (rc != S3IMPH_OK) return fail("open offsets: " + m, rc);
+  // beyond the header: what the reference checks per Get (reader.go:250-270), once
+  if (p->off.count != n + 1)
+    return fail("prefix_offsets holds " + std::to_string(p->off.count) + " entries, the index " + std::to_string(n) +
+                    " nodes",
+                S3IMPH_ERR_FORMAT);
+  const uint64_t* o = p->off.u64();
+  for (uint64_t i = 1; i <= n; ++i)
+    if (o[i] < o[i - 1]) return fail("prefix_offsets decreases at " + std::to_string(i), S3IMPH_ERR_FORMAT);
+  if (o[n] > size)
+    return fail("prefix_offsets ends at " + std::to_string(o[n]) + ", the blob holds " + std::to_string(size) +
+                    " bytes",
+                S3IMPH_ERR_FORMAT);
+  p->blob.assign((size + 7) / 8 + 1, 0);
+  if (size && std::fread(p->blob.data(), 1, size, f) != size)
+    return fail("open blob: read " + bp + ": " + std::strerror(errno), S3IMPH_ERR_IO);
+  p->present = true;
+  return S3IMPH_OK;
+}
+
 }  // namespace
 }  // namespace s3imph
 
@@ -754,6 +904,21 @@ struct s3imph_index {
   uint64_t* top_rp = nullptr;
   uint64_t top_rp_cap = 0;
   PrimTmp top_tmp;
+  // the stored prefixes (Open with S3IMPH_OPEN_PREFIXES: owned; s3imph_index_attach_prefixes: borrowed)
+  bool has_prefixes = false;
+  PrefixBlob pb;
+  // workspace of the last prefixes plan, apart from the descendants plan's: per row the source
+  // address and the length, the output offsets (rows + 1), scan block sums; the emit's chunk owners
+  uint64_t *nm_src = nullptr, *nm_len = nullptr, *nm_off = nullptr, *nm_sums = nullptr;
+  uint64_t nm_cap = 0;
+  uint64_t* nm_bounds = nullptr;
+  uint64_t nm_bounds_cap = 0;
+  bool have_names = false;
+  uint64_t names_rows = 0, names_total = 0;
+  // workspace of verify: the lookup's answers (n words), the reduction's three result words
+  uint64_t* vf_got = nullptr;
+  uint64_t vf_cap = 0;
+  unsigned long long* vf_res = nullptr;
 };
 
 namespace s3imph {
@@ -775,8 +940,10 @@ void index_free(s3imph_index* x) {
   for (void* p : x->owned)
     if (p) (void)hipFree(p);
   for (uint64_t** p : {&x->row_lo, &x->row_len, &x->U, &x->sums, &x->csum, &x->cbase, &x->csums2, &x->tier_table,
-                       &x->top_buf, &x->top_rp})
+                       &x->top_buf, &x->top_rp, &x->nm_src, &x->nm_len, &x->nm_off, &x->nm_sums, &x->nm_bounds,
+                       &x->vf_got})
     dfree(*p);
+  dfree(x->vf_res);
   x->top_tmp.release();
   delete x;
 }
@@ -972,22 +1139,87 @@ int top_locked(s3imph_index* x, int key, const s3imph_price_table& pt, uint32_t 
   return S3IMPH_OK;
 }
 
-}  // namespace
-}  // namespace s3imph
+// Every query over the stored prefixes on a handle without them (VerifyMPHF's words, mphf.go:374).
+int no_prefixes(const char* what, std::string* msg) {
+  *msg = std::string(what) + ": prefix blob not loaded";
+  return S3IMPH_ERR_STATE;
+}
 
-extern "C" {
+int names_plan_locked(s3imph_index* x, const uint64_t* d_qpos, uint64_t nq, uint64_t* d_out_offsets, uint32_t* d_found,
+                      uint64_t* total, hipStream_t s) {
+  x->have_names = false;
+  if (nq > x->nm_cap) {
+    x->nm_cap = 0;
+    dalloc(x->nm_src, nq);
+    dalloc(x->nm_len, nq);
+    dalloc(x->nm_off, nq + 1);
+    dalloc(x->nm_sums, scan_blocks(nq) + 1);
+    x->nm_cap = nq;
+  }
+  k_names_len<<<(unsigned)((nq + kQT - 1) / kQT), kQT, 0, s>>>(x->pb, x->a.n, d_qpos, nq, x->nm_src, x->nm_len, d_found);
+  launch_rows_scan(x->nm_len, nq, x->nm_sums, x->nm_off, d_out_offsets, s);
+  HIPCHECK(hipGetLastError());
+  uint64_t t = 0;
+  HIPCHECK(hipMemcpyAsync(&t, x->nm_off + nq, sizeof t, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  *total = t;
+  x->names_rows = nq;
+  x->names_total = t;
+  x->have_names = true;
+  return S3IMPH_OK;
+}
 
-int s3imph_index_open(int device, const char* dir, s3imph_index** out, char* err, size_t errlen) {
-  if (!out || !dir) {
+int names_fill_locked(s3imph_index* x, uint8_t* d_out, hipStream_t s, std::string* msg) {
+  const uint64_t total = x->names_total, nw = (total + 7) / 8, chunks = (nw + kChunkT - 1) / kChunkT;
+  if (chunks > 0x7fffffffull) {
+    *msg = "prefixes fill: more than 2^42 bytes in one batch";
+    return S3IMPH_ERR_INVALID;
+  }
+  grow(x->nm_bounds, x->nm_bounds_cap, chunks);
+  k_names_bounds<<<(unsigned)((chunks + kChunkT - 1) / kChunkT), kChunkT, 0, s>>>(x->nm_off, x->names_rows + 1, chunks,
+                                                                                 x->nm_bounds);
+  k_names_emit<<<(unsigned)chunks, kChunkT, 0, s>>>(x->pb, x->nm_off, x->nm_bounds, x->nm_src, x->names_rows, total,
+                                                    d_out);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(s));
+  return S3IMPH_OK;
+}
+
+// got[i] = Lookup(stored prefix i) for the whole index, reduced on the device.
+int verify_locked(s3imph_index* x, uint64_t* n_bad, uint64_t* first_bad, uint64_t* first_got, hipStream_t s) {
+  const uint64_t n = x->a.n;
+  grow(x->vf_got, x->vf_cap, n);
+  if (!x->vf_res) dalloc(x->vf_res, 3);
+  const int rc = s3imph_lookup_device(x->ctx, x->pb.blob, x->pb.off, n, x->a.fp, x->a.pos, n, x->vf_got, s);
+  if (rc != S3IMPH_OK) throw Fail{rc, std::string("verify: lookup: ") + s3imph_status_string(rc)};
+  HIPCHECK(hipMemsetAsync(x->vf_res, 0, 8, s));
+  HIPCHECK(hipMemsetAsync(x->vf_res + 1, 0xff, 16, s));
+  const uint64_t blocks = std::min<uint64_t>((n + kQT - 1) / kQT, 4096);
+  k_verify_reduce<<<(unsigned)blocks, kQT, 0, s>>>(x->vf_got, n, x->vf_res);
+  k_verify_got<<<1, 1, 0, s>>>(x->vf_got, x->vf_res);
+  HIPCHECK(hipGetLastError());
+  unsigned long long r[3] = {0, 0, 0};
+  HIPCHECK(hipMemcpyAsync(r, x->vf_res, sizeof r, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  *n_bad = r[0];
+  *first_bad = r[1];
+  *first_got = r[2];
+  return S3IMPH_OK;
+}
+
+int open_index(int device, const char* dir, unsigned flags, s3imph_index** out, char* err, size_t errlen) {
+  if (!out || !dir || (flags & ~(unsigned)S3IMPH_OPEN_PREFIXES)) {
     set_err(err, errlen, "invalid argument");
     return S3IMPH_ERR_INVALID;
   }
   *out = nullptr;
   try {
     HostIndex h;
+    HostPrefixes hp;
     std::string msg;
     // all validation on the host, before the device is selected or anything allocated on it
-    const int rc = load_host_index(dir, &h, &msg);
+    int rc = load_host_index(dir, &h, &msg);
+    if (rc == S3IMPH_OK && (flags & S3IMPH_OPEN_PREFIXES)) rc = load_host_prefixes(dir, h.n, &hp, &msg);
     if (rc != S3IMPH_OK) {
       set_err(err, errlen, msg);
       return rc;
@@ -1016,6 +1248,12 @@ int s3imph_index_open(int device, const char* dir, s3imph_index** out, char* err
         x->T = (uint32_t)h.tiers.size();
         for (uint32_t k = 0; k < x->T; ++k) x->tier_ids[k] = (uint8_t)h.tiers[k].id;
       }
+      if (hp.present) {
+        x->pb.off = upload(x, hp.off.u64(), h.n + 1);
+        x->pb.blob = reinterpret_cast<const uint8_t*>(upload(x, hp.blob.data(), hp.blob.size()));
+        x->pb.end8 = (hp.off.u64()[h.n] + 7) & ~7ull;
+        x->has_prefixes = true;
+      }
     } catch (const Fail& f) {
       index_free(x);
       set_err(err, errlen, f.msg);
@@ -1027,6 +1265,20 @@ int s3imph_index_open(int device, const char* dir, s3imph_index** out, char* err
     set_err(err, errlen, "open index: out of host memory");
     return S3IMPH_ERR_NOMEM;
   }
+}
+
+}  // namespace
+}  // namespace s3imph
+
+extern "C" {
+
+int s3imph_index_open(int device, const char* dir, s3imph_index** out, char* err, size_t errlen) {
+  return open_index(device, dir, 0, out, err, errlen);
+}
+
+int s3imph_index_open_flags(int device, const char* dir, unsigned flags, s3imph_index** out, char* err,
+                            size_t errlen) {
+  return open_index(device, dir, flags, out, err, errlen);
 }
 
 int s3imph_index_attach(int device, const s3imph_index_arrays* a, s3imph_index** out, char* err, size_t errlen) {
@@ -1274,6 +1526,114 @@ int s3imph_index_descendants_top(s3imph_index* x, int key, const s3imph_price_ta
     return retry_on_nomem(x->ctx, s, &msg, [&] {
       return top_locked(x, key, cost ? *pt : none, k, d_top_pos, d_top_key, d_top_n, s, &msg);
     });
+  });
+}
+
+int s3imph_index_attach_prefixes(s3imph_index* x, const uint8_t* d_blob, const uint64_t* d_offsets) {
+  if (!x) return S3IMPH_ERR_INVALID;
+  return index_entry(x, [&](std::string& msg) -> int {
+    if (!d_blob || !d_offsets) {
+      msg = "attach prefixes: invalid argument";
+      return S3IMPH_ERR_INVALID;
+    }
+    hipStream_t s = use_device(x->device, nullptr, x->ctx->own_stream);
+    uint64_t end = 0;
+    HIPCHECK(hipMemcpyAsync(&end, d_offsets + x->a.n, sizeof end, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    x->have_names = false;  // its source addresses were the earlier blob's
+    x->pb.blob = d_blob;
+    x->pb.off = d_offsets;
+    x->pb.end8 = (end + 7) & ~7ull;
+    x->has_prefixes = true;
+    return S3IMPH_OK;
+  });
+}
+
+int s3imph_index_has_prefixes(const s3imph_index* x) { return x && x->has_prefixes ? 1 : 0; }
+
+int s3imph_index_prefixes_plan(s3imph_index* x, const uint64_t* d_qpos, uint64_t nq, uint64_t* d_out_offsets,
+                               uint32_t* d_found, uint64_t* total, void* stream) {
+  if (!x || !total) return S3IMPH_ERR_INVALID;
+  *total = 0;
+  return index_entry(x, [&](std::string& msg) -> int {
+    if (!x->has_prefixes) return no_prefixes("prefixes plan", &msg);
+    if (nq && (!d_qpos || !d_out_offsets)) {
+      msg = "prefixes plan: invalid argument";
+      return S3IMPH_ERR_INVALID;
+    }
+    if (nq >= (1ull << 31)) {
+      msg = "prefixes plan: 2^31 positions or more in one batch";
+      return S3IMPH_ERR_INVALID;
+    }
+    x->have_names = false;  // whatever is thrown from here on leaves no plan
+    if (nq == 0) {
+      if (d_out_offsets) {
+        hipStream_t s0 = use_device(x->device, stream, x->ctx->own_stream);
+        HIPCHECK(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), s0));
+        HIPCHECK(hipStreamSynchronize(s0));
+      }
+      x->names_rows = x->names_total = 0;
+      x->have_names = true;
+      return S3IMPH_OK;
+    }
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
+    return retry_on_nomem(x->ctx, s, &msg,
+                          [&] { return names_plan_locked(x, d_qpos, nq, d_out_offsets, d_found, total, s); });
+  });
+}
+
+int s3imph_index_prefixes_fill(s3imph_index* x, uint8_t* d_out, uint64_t cap, void* stream) {
+  if (!x) return S3IMPH_ERR_INVALID;
+  return index_entry(x, [&](std::string& msg) -> int {
+    if (!x->has_prefixes) return no_prefixes("prefixes fill", &msg);
+    if (!x->have_names) {
+      msg = "prefixes fill: no plan";
+      return S3IMPH_ERR_STATE;
+    }
+    const uint64_t need = (x->names_total + 7) & ~7ull;
+    if (cap < need || (need && !d_out)) {
+      msg = "prefixes fill: out needs " + std::to_string(need) + " bytes";
+      return S3IMPH_ERR_INVALID;
+    }
+    if (need == 0) return S3IMPH_OK;
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
+    return retry_on_nomem(x->ctx, s, &msg, [&] { return names_fill_locked(x, d_out, s, &msg); });
+  });
+}
+
+int s3imph_index_lookup_verify_device(s3imph_index* x, const uint8_t* d_blob, const uint64_t* d_offsets, uint64_t nq,
+                                      uint64_t* d_pos_out, void* stream) {
+  if (!x || (nq && (!d_blob || !d_offsets || !d_pos_out))) return S3IMPH_ERR_INVALID;
+  return index_entry(x, [&](std::string& msg) -> int {
+    if (!x->has_prefixes) return no_prefixes("lookup verify", &msg);
+    if (nq == 0) return S3IMPH_OK;
+    if (nq >= (1ull << 39)) {
+      msg = "lookup verify: 2^39 keys or more in one batch";
+      return S3IMPH_ERR_INVALID;
+    }
+    const int rc = s3imph_lookup_device(x->ctx, d_blob, d_offsets, nq, x->a.fp, x->a.pos, x->a.n, d_pos_out, stream);
+    if (rc != S3IMPH_OK) {
+      msg = std::string("lookup verify: ") + s3imph_status_string(rc);
+      return rc;
+    }
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
+    k_lookup_verify<<<(unsigned)((nq + kQT - 1) / kQT), kQT, 0, s>>>(x->pb, x->a.n, d_blob, d_offsets, nq, d_pos_out);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(s));
+    return S3IMPH_OK;
+  });
+}
+
+int s3imph_index_verify_device(s3imph_index* x, uint64_t* n_bad, uint64_t* first_bad, uint64_t* first_got,
+                               void* stream) {
+  if (!x || !n_bad || !first_bad || !first_got) return S3IMPH_ERR_INVALID;
+  *n_bad = 0;
+  *first_bad = *first_got = ~0ull;
+  return index_entry(x, [&](std::string& msg) -> int {
+    if (!x->has_prefixes) return no_prefixes("verify", &msg);
+    if (x->a.n == 0) return S3IMPH_OK;
+    hipStream_t s = use_device(x->device, stream, x->ctx->own_stream);
+    return retry_on_nomem(x->ctx, s, &msg, [&] { return verify_locked(x, n_bad, first_bad, first_got, s); });
   });
 }
 

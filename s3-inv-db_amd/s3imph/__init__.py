@@ -97,7 +97,11 @@ EXPORTS = (
     "s3imph_merge_rows_host", "s3imph_index_from_rows_host",
     "s3imph_rowset_new", "s3imph_rowset_add_objects", "s3imph_rowset_add_csv", "s3imph_rowset_add_rows",
     "s3imph_rowset_runs", "s3imph_rowset_rows", "s3imph_rowset_build", "s3imph_rowset_close",
+    "s3imph_index_open_flags", "s3imph_index_attach_prefixes", "s3imph_index_has_prefixes",
+    "s3imph_index_prefixes_plan", "s3imph_index_prefixes_fill", "s3imph_index_lookup_verify_device",
+    "s3imph_index_verify_device",
 )
+OPEN_PREFIXES = 1  # S3IMPH_OPEN_PREFIXES
 MERGE_MAX_RUNS = 64  # S3IMPH_MERGE_MAX_RUNS
 NUM_TIERS = 12  # S3IMPH_NUM_TIERS
 
@@ -347,6 +351,13 @@ def _load():
         "s3imph_rowset_rows": (u64, [vp]),
         "s3imph_rowset_build": (i32, [vp, cp, cp, sz]),
         "s3imph_rowset_close": (i32, [vp]),
+        "s3imph_index_open_flags": (i32, [i32, cp, ctypes.c_uint, P(vp), cp, sz]),
+        "s3imph_index_attach_prefixes": (i32, [vp, vp, vp]),
+        "s3imph_index_has_prefixes": (i32, [vp]),
+        "s3imph_index_prefixes_plan": (i32, [vp, vp, u64, vp, vp, P(u64), vp]),
+        "s3imph_index_prefixes_fill": (i32, [vp, vp, u64, vp]),
+        "s3imph_index_lookup_verify_device": (i32, [vp, vp, vp, u64, vp, vp]),
+        "s3imph_index_verify_device": (i32, [vp, P(u64), P(u64), P(u64), vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -421,6 +432,29 @@ def _dev_ptr(t) -> ctypes.c_void_p | None:
     if isinstance(t, int):
         return ctypes.c_void_p(t)
     return ctypes.c_void_p(t.data_ptr())
+
+
+_GO_ESCAPES = {0x07: "\\a", 0x08: "\\b", 0x0c: "\\f", 0x0a: "\\n", 0x0d: "\\r", 0x09: "\\t", 0x0b: "\\v",
+               0x22: '\\"', 0x5c: "\\\\"}
+
+
+def _go_quote(b: bytes) -> str:
+    """fmt's %q of a string (strconv.Quote): printable runes as they are, the C escapes, \\x for
+    other control characters and for bytes that are not UTF-8, \\u / \\U for the rest."""
+    out = []
+    for ch in b.decode("utf-8", errors="surrogateescape"):
+        c = ord(ch)
+        if 0xdc80 <= c <= 0xdcff:  # a byte that was not UTF-8
+            out.append("\\x%02x" % (c - 0xdc00))
+        elif c in _GO_ESCAPES:
+            out.append(_GO_ESCAPES[c])
+        elif ch.isprintable():
+            out.append(ch)
+        elif c < 0x20 or c == 0x7f:
+            out.append("\\x%02x" % c)
+        else:
+            out.append("\\u%04x" % c if c < 0x10000 else "\\U%08x" % c)
+    return '"' + "".join(out) + '"'
 
 
 def keys_to_blob(keys) -> tuple[np.ndarray, np.ndarray]:
@@ -1504,7 +1538,11 @@ class Index:
         idx.stats_for_prefix(keys)                # StatsForPrefix (:146)
         idx.descendants_at_depth(pos, rel)        # DescendantsAtDepth[Filtered] (:206, :277)
         idx.descendants_up_to_depth(pos, max_rel) # DescendantsUpToDepth (:239)
-        idx.prefix_string(pos)                    # PrefixString (:179)
+        idx.prefix_string(pos)                    # PrefixString (:179), one position from the host files
+        idx = Index(dir, prefixes=True)           # ... with the prefix blob in HBM (OpenMPHF, mphf.go:226-238)
+        idx.prefix_strings(pos)                   # PrefixString for a batch, None where out of bounds
+        idx.lookup_verify(keys)                   # MPHF.LookupWithVerify (mphf.go:306)
+        idx.verify()                              # VerifyMPHF (mphf.go:372)
         idx.has_tier_data(), idx.present_tiers()  # HasTierData (:360), the manifest's tiers
         idx.tier_breakdown_all(pos)               # TierBreakdownAll (:380)
         idx.tier_breakdown(pos)                   # TierBreakdown (:368)
@@ -1514,10 +1552,14 @@ class Index:
     Positions are given as a sequence, a numpy array or a device tensor (int64 holding the
     u64 bits).  object_count.u64 / total_bytes.u64 are optional (zeros without them)."""
 
-    def __init__(self, dir_: str, device: int = 0):
+    def __init__(self, dir_: str, device: int = 0, prefixes: bool = False):
         err = ctypes.create_string_buffer(1024)
         h = ctypes.c_void_p()
-        _check(LIB.s3imph_index_open(device, os.fsencode(dir_), ctypes.byref(h), err, 1024), err)
+        if prefixes:  # s3imph_index_open_flags: the prefix blob in HBM too, when the directory has one
+            _check(LIB.s3imph_index_open_flags(device, os.fsencode(dir_), OPEN_PREFIXES, ctypes.byref(h), err, 1024),
+                   err)
+        else:
+            _check(LIB.s3imph_index_open(device, os.fsencode(dir_), ctypes.byref(h), err, 1024), err)
         self._h = h
         self._init(device, dir_, None)
 
@@ -1527,6 +1569,7 @@ class Index:
         self.dir = dir_
         self._keep = keep  # borrowed device tensors stay alive with the handle
         self._prefixes = None
+        self._keep_prefixes = None
         self.count = int(LIB.s3imph_index_count(self._h))
         self.max_depth = int(LIB.s3imph_index_max_depth(self._h))
 
@@ -1815,11 +1858,93 @@ class Index:
             raise MPHFError(ERR_INVALID, f"get prefix for pos {pos}: position out of bounds")
         return bytes(blob[int(offs[pos]):int(offs[pos + 1])]).decode(errors="surrogateescape")
 
+    # -- the prefix blob in HBM: PrefixString for a batch, LookupWithVerify, VerifyMPHF --------
+    def attach_prefixes(self, blob, offsets) -> None:
+        """s3imph_index_attach_prefixes: the stored prefixes of a from_arrays handle, as device
+        tensors (count + 1 offsets; the blob readable up to its last offset rounded up to 8),
+        borrowed for the life of the handle.  A second call replaces the first."""
+        self._fail(LIB.s3imph_index_attach_prefixes(self._h, _dev_ptr(blob), _dev_ptr(offsets)), "attach prefixes")
+        self._keep_prefixes = (blob, offsets)
+
+    def has_prefixes(self) -> bool:
+        return bool(LIB.s3imph_index_has_prefixes(self._h))
+
+    def prefixes_plan(self, pos, stream=None):
+        """s3imph_index_prefixes_plan: (out_offsets int64[nq + 1], found int32[nq], total), the
+        tensors on the device."""
+        import torch
+        with _torch_on(stream, self.dev):
+            d_pos = self._pos_dev(pos)
+            nq = int(d_pos.shape[0])
+            offs = torch.zeros(nq + 1, dtype=torch.int64, device=self.dev)
+            found = torch.zeros(max(nq, 1), dtype=torch.int32, device=self.dev)
+        total = ctypes.c_uint64()
+        self._fail(LIB.s3imph_index_prefixes_plan(self._h, _dev_ptr(d_pos), nq, _dev_ptr(offs), _dev_ptr(found),
+                                                  ctypes.byref(total), _stream_ptr(stream)), "prefixes plan")
+        return offs, found[:nq], int(total.value)
+
+    def prefixes_fill(self, total: int, out=None, stream=None):
+        """s3imph_index_prefixes_fill of the last prefixes plan: a uint8 tensor of round_up(total,
+        8) bytes, one word when total is 0 (`out`, when given: a uint8 device tensor of any
+        alignment and at least round_up(total, 8) bytes)."""
+        import torch
+        if out is None:
+            out = torch.empty(max((total + 7) // 8 * 8, 8), dtype=torch.uint8, device=self.dev)
+        self._fail(LIB.s3imph_index_prefixes_fill(self._h, _dev_ptr(out), int(out.numel()), _stream_ptr(stream)),
+                   "prefixes fill")
+        return out
+
+    def prefixes_device(self, pos, stream=None):
+        """PrefixString (index.go:179) for a batch of positions (a sequence, or a device tensor such as
+        descendants_fill's output): (out_offsets int64[nq + 1], found int32[nq], out_bytes uint8),
+        all on the device; row q is out_bytes[out_offsets[q]:out_offsets[q + 1]], and (out_bytes,
+        out_offsets) goes straight back into lookup_device."""
+        offs, found, total = self.prefixes_plan(pos, stream)
+        return offs, found, self.prefixes_fill(total, stream=stream)
+
+    def prefix_strings(self, pos) -> list:
+        """PrefixString per position as bytes; None where the reference returns ErrBoundsCheck."""
+        offs, found, out = self.prefixes_device(pos)
+        o, f, b = offs.cpu().numpy(), found.cpu().numpy(), out.cpu().numpy().tobytes()
+        return [b[o[q]:o[q + 1]] if f[q] else None for q in range(len(f))]
+
+    def lookup_verify_device(self, d_blob, d_offsets, nq: int, stream=None):
+        """s3imph_index_lookup_verify_device over a query blob in HBM: as lookup_device, 2^64-1
+        unless the stored prefix at the position equals the query."""
+        import torch
+        res = torch.empty(max(nq, 1), dtype=torch.int64, device=self.dev)
+        self._fail(LIB.s3imph_index_lookup_verify_device(self._h, _dev_ptr(d_blob), _dev_ptr(d_offsets), nq,
+                                                         _dev_ptr(res), _stream_ptr(stream)), "lookup verify")
+        return res[:nq]
+
+    def lookup_verify(self, keys) -> np.ndarray:
+        """LookupWithVerify (mphf.go:306-320) of a batch: pos per key, or 2^64-1."""
+        return self.lookup_verify_device(*self._keys_dev(*keys_to_blob(keys))).cpu().numpy().view(np.uint64)
+
+    def verify_device(self, stream=None) -> tuple:
+        """s3imph_index_verify_device: (n_bad, first_bad, first_got)."""
+        r = [ctypes.c_uint64() for _ in range(3)]
+        self._fail(LIB.s3imph_index_verify_device(self._h, ctypes.byref(r[0]), ctypes.byref(r[1]), ctypes.byref(r[2]),
+                                                  _stream_ptr(stream)), "verify")
+        return tuple(int(v.value) for v in r)
+
+    def verify(self) -> None:
+        """VerifyMPHF (mphf.go:372-393): raises MPHFError(ERR_INTERNAL) with the reference's text for
+        the first stored prefix that does not look up to its own index."""
+        n_bad, i, got = self.verify_device()
+        if n_bad == 0:
+            return
+        q = _go_quote(self.prefix_strings([i])[0])
+        if got == (1 << 64) - 1:
+            raise MPHFError(ERR_INTERNAL, f"lookup failed for prefix {q} at pos {i}")
+        raise MPHFError(ERR_INTERNAL, f"lookup returned wrong pos for {q}: got {got}, want {i}")
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             LIB.s3imph_index_close(self._h)
             self._h = None
             self._keep = None
+            self._keep_prefixes = None
 
     def __enter__(self):
         return self
