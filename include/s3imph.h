@@ -790,8 +790,8 @@ int s3imph_index_from_unsorted_objects_host(int device, const uint8_t *keys, con
  *     White space is the ASCII set of s3imph_tier_from_s3 — one rule for tier names, header
  *     names and sizes; the reference trims Unicode white space as well.
  *
- *     Out of scope: gzip (the caller inflates), Parquet, a listing larger than one GPU's memory,
- *     the multi-GPU builds.
+ *     Out of scope: Parquet, a listing larger than one GPU's memory, the multi-GPU builds
+ *     (gzip files: section 5j).
  *
  *     Memory: the scratch lives in ctx, grows on demand and is released by
  *     s3imph_release_workspaces: 1/16 byte per input byte (a 2-byte state map per 32-byte run; 11
@@ -1098,6 +1098,90 @@ uint64_t s3imph_rowset_runs(const s3imph_rowset *rs);
 uint64_t s3imph_rowset_rows(const s3imph_rowset *rs);
 int s3imph_rowset_build(s3imph_rowset *rs, const char *out_dir, char *err, size_t errlen);
 int s3imph_rowset_close(s3imph_rowset *rs);
+
+/* ------------------------------------------------------------------------
+ * 5j. gzip files inflated on the GPU, and the index built from .csv.gz inventory files: what
+ *     pgzip.NewReader / gzip.NewReader do in front of the CSV readers (pkg/inventory/unified.go:93-103,
+ *     reader.go:81-86, :216-221).  Parity is "vs the RFCs, checked against zlib": RFC 1951,
+ *     RFC 1952 and compress/gzip's behaviour as stated here.
+ *
+ *     A gzip file is one or more members back to back (Go's multistream default).  Per member:
+ *     magic 1f 8b and CM = 8, anything else "invalid header"; FEXTRA, FNAME and FCOMMENT are
+ *     skipped; FHCRC (the low 16 bits of the CRC-32 of the header bytes) is verified, a mismatch
+ *     is "invalid header"; reserved flag bits are ignored; a raw DEFLATE stream; CRC-32 and ISIZE,
+ *     little-endian.  After a member the end of the input is a clean end, and anything else must
+ *     be another member header: trailing bytes that are none, zero padding included, are "invalid
+ *     header".  A zero-length file is "unexpected EOF".  A member's window starts empty: a
+ *     distance that reaches before the member's own first byte is corrupt.
+ *
+ *     DEFLATE in full: stored blocks (LEN 0 to 65535, NLEN checked), fixed and dynamic Huffman
+ *     blocks (the repeat symbols 16 - 18 may run across the literal/length - distance boundary),
+ *     code lengths up to 15, lengths up to 258, distances up to 32768, overlapping copies.  A set
+ *     of code lengths is refused when over-subscribed, and when incomplete unless it is a single
+ *     code of length 1 or empty; a dynamic block without an end-of-block code is refused; block
+ *     type 3, literal/length symbols 286 and 287 and distance symbols 30 and 31 are corrupt.
+ *
+ *     Out of scope: zlib and raw-deflate containers, preset dictionaries, parallel decoding inside
+ *     one member (the parallelism is across files: a wave per file), returning the header fields.
+ * ------------------------------------------------------------------------ */
+enum { S3IMPH_GZ_OK = 0, S3IMPH_GZ_MORE = 1, S3IMPH_GZ_EOF = 2, S3IMPH_GZ_HEADER = 3,
+       S3IMPH_GZ_DATA = 4, S3IMPH_GZ_CHECKSUM = 5 };
+
+typedef struct s3imph_gunzip_info {   /* 32 bytes */
+    uint64_t out_bytes;  /* inflated bytes of all members, counted past the room given as well */
+    uint64_t in_used;    /* gzip bytes consumed; == the file's length when status is OK or MORE */
+    uint32_t members;
+    uint32_t status;     /* S3IMPH_GZ_* */
+    uint32_t crc32;      /* the CRC-32 the trailers promise for the whole output */
+    uint32_t reserved;   /* 0 */
+} s3imph_gunzip_info;
+
+/* The decoder's geometry, for tests that place events on the edges: the input stage holds
+ * *in_chunk_bytes of a file, a batch *batch_symbols decoded symbols, and the grid is at most
+ * CUs x *waves_per_cu waves (more files than that make the ticket loop wrap). */
+void s3imph_gunzip_geometry(uint32_t *in_chunk_bytes, uint32_t *batch_symbols, uint32_t *waves_per_cu);
+
+/* Host only: the room to offer a file, min(ISIZE read from its last four bytes, 1032 * len + 64),
+ * 0 for len < 18.  1032 : 1 is DEFLATE's largest expansion, so a lying trailer cannot ask for
+ * 4 GiB; for a single-member file under 4 GiB the hint is exact. */
+uint64_t s3imph_gunzip_room_hint(const uint8_t *gz, uint64_t len);
+
+/* n_files gzip files in HBM, one launch.  File i is d_gz[gz_offsets[i] .. gz_offsets[i+1]) at any
+ * byte alignment and may write only d_out[out_offsets[i] .. out_offsets[i+1]); no byte outside
+ * that range is written, whatever the input holds.  Returns S3IMPH_OK when it ran; the verdict per
+ * file is info[i].status: OK; MORE (the file needs out_bytes of room; the bytes that fit were
+ * written correctly); EOF, HEADER, DATA, CHECKSUM (the contents of the file's range are
+ * unspecified).  The CRC-32 of the text is computed on the device and compared with the trailers'
+ * for every file that is OK.  Null arguments with n_files > 0, non-monotonic offsets and
+ * n_files >= 2^31 are S3IMPH_ERR_INVALID before any device work; n_files == 0 is OK without any.
+ * Synchronous on `stream`. */
+int s3imph_gunzip_device(s3imph_ctx *ctx, const uint8_t *d_gz, const uint64_t *gz_offsets /* host, n+1 */,
+                         uint64_t n_files, uint8_t *d_out, const uint64_t *out_offsets /* host, n+1 */,
+                         s3imph_gunzip_info *info /* host, n */, void *stream);
+
+/* The same from host memory: H2D of the compressed bytes, one launch with the room hints, the
+ * files that reported MORE once more with their exact room, D2H.  out[i] is allocated by the
+ * library (release each with s3imph_free), out_len[i] its length; info (nullable) as above.  A bad
+ * file is S3IMPH_ERR_FORMAT, worded "gzip: file <i>: unexpected EOF | invalid header | corrupt
+ * input | invalid checksum" for the lowest such i, and leaves every out[i] NULL. */
+int s3imph_gunzip_host(int device, const uint8_t *const *gz, const uint64_t *gz_len, uint64_t n_files,
+                       uint8_t **out /* n pointers, each s3imph_free */, uint64_t *out_len,
+                       s3imph_gunzip_info *info /* nullable */, char *err, size_t errlen);
+
+/* s3imph_index_from_csv_host over .csv.gz files: consecutive files are uploaded compressed and
+ * inflated on the device in groups of about group_bytes (compressed bytes plus room hints; 0: the
+ * library's default; a file larger than that is a group of its own; the result does not depend on
+ * it), then parsed file by file from HBM as the CSV call parses them.  A bad gzip file fails the
+ * call as in s3imph_gunzip_host, before anything is written.  A missing out_dir is S3IMPH_ERR_IO
+ * before the device is selected; the out-of-memory retry of the host builds applies. */
+int s3imph_index_from_csv_gz_host(int device, const uint8_t *const *gz, const uint64_t *gz_len, uint64_t n_files,
+                                  const s3imph_csv_schema *schema, int with_tiers, uint32_t max_depth,
+                                  uint64_t group_bytes /* 0: default */, const char *out_dir,
+                                  s3imph_csv_info *info_total, char *err, size_t errlen);
+
+/* s3imph_rowset_add_csv over .csv.gz files; a bad gzip file adds no run. */
+int s3imph_rowset_add_csv_gz(s3imph_rowset *rs, const uint8_t *const *gz, const uint64_t *gz_len, uint64_t n_files,
+                             const s3imph_csv_schema *schema, uint64_t group_bytes, char *err, size_t errlen);
 
 /* ------------------------------------------------------------------------
  * 6. Deterministic synthetic prefix sets (bench/test support, not on the path).

@@ -973,6 +973,7 @@ int s3imph::index_from_objects(int device, const uint8_t* keys, const uint64_t* 
   IndexHostArrays h;
   uint64_t csv_bytes = 0;
   for (uint64_t i = 0; csv && i < csv->n_files; ++i) csv_bytes += csv->len[i];
+  if (csv && csv->gz) csv_bytes += csv->n_files;  // a zero-length gzip file is an error the device reports
   if (m || csv_bytes) {
     // one device residency: the rows stay in HBM from the aggregation to the last array
     const int rc = host_entry(

@@ -642,18 +642,16 @@ void keep_grow(DevGuard& g, T*& p, uint64_t& cap, uint64_t used, uint64_t need, 
 // The CSV buffers of `f`, each parsed on its own, appended in order into one listing in HBM
 // (owned by g; the keys readable 16 bytes past their end rounded up to 8, as upload_keys leaves
 // them).  The first file's yield per byte sizes the arrays for all of them; they grow when a later
-// file yields more.  *m == 0: no array is made.
+// file yields more.  *m == 0: no array is made.  With f.gz the buffers are gzip files: only the
+// source of each file's text changes (s3imph_inflate.hip), the plan / fill loop is the same.
 int csv_listing(s3imph_ctx* c, DevGuard& g, const CsvFiles& f, uint8_t*& d_keys, uint64_t*& d_koff,
                 uint64_t*& d_sizes, uint8_t*& d_tiers, uint64_t* m, hipStream_t s, std::string* msg) {
   uint64_t cap_keys = 0, cap_off = 0, cap_sizes = 0, cap_tiers = 0, n = 0, nbytes = 0, left = 0;
   for (uint64_t i = 0; i < f.n_files; ++i) left += f.len[i];
   s3imph_csv_info total{};
-  for (uint64_t i = 0; i < f.n_files; ++i) {
-    const uint64_t len = f.len[i];
-    if (len == 0) continue;
-    uint8_t* d_csv = nullptr;
-    g.make(d_csv, (len + 7) & ~7ull);
-    staged_copy(c, true, d_csv, f.csv[i], len);
+  // One file's text in HBM (len bytes, readable to round_up(len, 8)) appended to the listing;
+  // `weight` is the file's share of `left` (its bytes as they were given: compressed with gz).
+  auto append = [&](const uint8_t* d_csv, uint64_t len, uint64_t weight, bool last) -> int {
     s3imph_csv_info info;
     const int rc = csv_plan(c, d_csv, len, *f.schema, &info, s, msg);
     if (rc != S3IMPH_OK) return rc;
@@ -664,9 +662,9 @@ int csv_listing(s3imph_ctx* c, DevGuard& g, const CsvFiles& f, uint8_t*& d_keys,
     }
     if (info.n_objects) {
       // this file's yield, scaled to the bytes still to come, with a twentieth to spare
-      const double scale = 1.05 * (double)left / (double)len;
-      const uint64_t want_n = n + (i + 1 < f.n_files ? (uint64_t)(info.n_objects * scale) : info.n_objects);
-      const uint64_t want_b = nbytes + (i + 1 < f.n_files ? (uint64_t)(info.key_bytes * scale) : info.key_bytes);
+      const double scale = 1.05 * (double)left / (double)std::max<uint64_t>(weight, 1);
+      const uint64_t want_n = n + (!last ? (uint64_t)(info.n_objects * scale) : info.n_objects);
+      const uint64_t want_b = nbytes + (!last ? (uint64_t)(info.key_bytes * scale) : info.key_bytes);
       // the estimate counts only for the first allocation; afterwards an array grows when it must
       const uint64_t est_n = cap_off ? 0 : want_n, est_b = cap_keys ? 0 : want_b;
       const uint64_t need_n = std::max<uint64_t>(n + info.n_objects, est_n);
@@ -682,8 +680,44 @@ int csv_listing(s3imph_ctx* c, DevGuard& g, const CsvFiles& f, uint8_t*& d_keys,
       nbytes += info.key_bytes;
     }
     c->csv->have_plan = false;  // the text goes away here
+    left -= weight;
+    return S3IMPH_OK;
+  };
+  // gzip files: groups of consecutive files, in input order, each uploaded compressed, inflated in
+  // one launch and parsed file by file from HBM
+  for (uint64_t lo = 0; f.gz && lo < f.n_files;) {
+    const uint64_t budget = f.group_bytes ? f.group_bytes : kGzGroupBytes;
+    uint64_t hi = lo, sum = 0;
+    while (hi < f.n_files) {
+      const uint64_t cost = f.len[hi] + gunzip_room_hint(f.csv[hi], f.len[hi]);
+      if (hi > lo && (cost > budget || sum > budget - cost)) break;
+      sum += std::min(cost, budget);
+      ++hi;
+    }
+    GzTexts t;
+    const int rc = gunzip_group(c, g, f.csv, f.len, lo, hi, &t, s, msg);
+    if (rc != S3IMPH_OK) return rc;
+    for (uint64_t i = lo; i < hi; ++i) {
+      const uint64_t len = t.info[i - lo].out_bytes;
+      if (len == 0) {
+        left -= f.len[i];
+        continue;
+      }
+      const int rc2 = append(t.text[i - lo], len, f.len[i], i + 1 == f.n_files);
+      if (rc2 != S3IMPH_OK) return rc2;
+    }
+    gunzip_group_free(g, &t);
+    lo = hi;
+  }
+  for (uint64_t i = 0; !f.gz && i < f.n_files; ++i) {
+    const uint64_t len = f.len[i];
+    if (len == 0) continue;
+    uint8_t* d_csv = nullptr;
+    g.make(d_csv, (len + 7) & ~7ull);
+    staged_copy(c, true, d_csv, f.csv[i], len);
+    const int rc = append(d_csv, len, len, i + 1 == f.n_files);
+    if (rc != S3IMPH_OK) return rc;
     g.drop(d_csv);
-    left -= len;
   }
   if (f.total) *f.total = total;
   *m = n;
@@ -785,6 +819,22 @@ int s3imph_index_from_csv_host(int device, const uint8_t* const* csv, const uint
     if (csv_len[i] && !csv[i]) return S3IMPH_ERR_INVALID;
   s3imph_csv_info total{};
   const CsvFiles f{csv, csv_len, n_files, schema, with_tiers != 0, &total};
+  const int rc = index_from_objects(device, nullptr, nullptr, nullptr, nullptr, 0, max_depth, out_dir, true, err,
+                                    errlen, &f);
+  if (info_total) *info_total = total;
+  return rc;
+}
+
+int s3imph_index_from_csv_gz_host(int device, const uint8_t* const* gz, const uint64_t* gz_len, uint64_t n_files,
+                                  const s3imph_csv_schema* schema, int with_tiers, uint32_t max_depth,
+                                  uint64_t group_bytes, const char* out_dir, s3imph_csv_info* info_total, char* err,
+                                  size_t errlen) {
+  if (!schema || !out_dir || (n_files && (!gz || !gz_len)) || schema->key_col < 0 || schema->size_col < 0)
+    return S3IMPH_ERR_INVALID;
+  for (uint64_t i = 0; i < n_files; ++i)
+    if (gz_len[i] && !gz[i]) return S3IMPH_ERR_INVALID;
+  s3imph_csv_info total{};
+  const CsvFiles f{gz, gz_len, n_files, schema, with_tiers != 0, &total, true, group_bytes};
   const int rc = index_from_objects(device, nullptr, nullptr, nullptr, nullptr, 0, max_depth, out_dir, true, err,
                                     errlen, &f);
   if (info_total) *info_total = total;

@@ -439,7 +439,8 @@ int csv_fill(s3imph_ctx* c, uint8_t* keys, uint64_t keys_cap, uint64_t key_base,
              uint8_t* tiers, hipStream_t s, std::string* msg);
 void csv_scratch_free(s3imph_ctx* c);
 // Host CSV buffers to one listing in HBM, file after file (owned by g; *m objects; *total sums
-// the files' infos when given).
+// the files' infos when given).  With `gz` the buffers are gzip files, inflated on the device in
+// groups of consecutive files of about group_bytes (compressed bytes plus room; 0: kGzGroupBytes).
 struct CsvFiles {
   const uint8_t* const* csv;
   const uint64_t* len;
@@ -447,7 +448,33 @@ struct CsvFiles {
   const s3imph_csv_schema* schema;
   bool with_tiers;
   s3imph_csv_info* total;
+  bool gz = false;
+  uint64_t group_bytes = 0;
 };
+// gzip (s3imph_inflate.hip).  A group's footprint in HBM beside the listing: at 8 : 1 and 4 MiB of
+// text per file 2 GiB hold some 450 files, a ninth of a full grid's waves, and stay a small share
+// of HBM next to the listing arrays that grow with every file.
+constexpr uint64_t kGzGroupBytes = 2ull << 30;
+struct GzFile {
+  uint64_t in_off, in_len;  // the file's bytes in the compressed buffer
+  uint64_t out_off, room;   // where its text goes, and how many bytes may be written
+};
+// files[i] of d_gz inflated into d_out; info: n host entries.  Waits for the stream; throws Fail.
+void gunzip_files(s3imph_ctx* c, const uint8_t* d_gz, uint8_t* d_out, const GzFile* files, uint64_t n,
+                  s3imph_gunzip_info* info, hipStream_t s);
+uint64_t gunzip_room_hint(const uint8_t* gz, uint64_t len);
+// Host gzip files [lo, hi) uploaded packed and inflated with their room hints, the files that
+// needed more again with their exact room: text[i] (8-byte aligned, readable to round_up(its
+// length, 8)) and info[i] per file, the buffers owned by g.  A bad file: S3IMPH_ERR_FORMAT and
+// "gzip: file <i>: ..." for the lowest i.
+struct GzTexts {
+  std::vector<const uint8_t*> text;
+  std::vector<s3imph_gunzip_info> info;
+  uint8_t *d_gz = nullptr, *d_out = nullptr, *d_again = nullptr;
+};
+int gunzip_group(s3imph_ctx* c, DevGuard& g, const uint8_t* const* gz, const uint64_t* gz_len, uint64_t lo,
+                 uint64_t hi, GzTexts* t, hipStream_t s, std::string* msg);
+void gunzip_group_free(DevGuard& g, GzTexts* t);
 int csv_listing(s3imph_ctx* c, DevGuard& g, const CsvFiles& f, uint8_t*& d_keys, uint64_t*& d_koff,
                 uint64_t*& d_sizes, uint8_t*& d_tiers, uint64_t* m, hipStream_t s, std::string* msg);
 // The prefix rows of a listing or of a merge, left in HBM (owned by a DevGuard).

@@ -54,7 +54,8 @@ int host_call(const char* prefix, char* err, size_t errlen, F&& f) {
     if (rc != S3IMPH_OK) set_err(err, errlen, msg);
     return rc;
   } catch (const Fail& e) {
-    const bool worded = e.msg.compare(0, 6, "sort: ") == 0 || e.msg.compare(0, 5, "csv: ") == 0;
+    const bool worded = e.msg.compare(0, 6, "sort: ") == 0 || e.msg.compare(0, 5, "csv: ") == 0 ||
+                        e.msg.compare(0, 6, "gzip: ") == 0;
     set_err(err, errlen, worded ? e.msg : prefix + e.msg);
     return e.code;
   } catch (const std::bad_alloc&) {

@@ -728,6 +728,7 @@ int rowset_add_chunk(s3imph_rowset* rs, const uint8_t* keys, const uint64_t* kof
   std::lock_guard<std::mutex> hold(rs->mu);
   uint64_t csv_bytes = 0;
   for (uint64_t i = 0; csv && i < csv->n_files; ++i) csv_bytes += csv->len[i];
+  if (csv && csv->gz) csv_bytes += csv->n_files;  // a zero-length gzip file is an error the device reports
   if (!m && !csv_bytes) return S3IMPH_OK;  // a chunk without an object adds no run
   if (csv) tiers = rs->tiers ? &kWanted : nullptr;
   return host_entry(
@@ -863,6 +864,16 @@ int s3imph_rowset_add_csv(s3imph_rowset* rs, const uint8_t* const* csv, const ui
   for (uint64_t i = 0; i < n_files; ++i)
     if (csv_len[i] && !csv[i]) return S3IMPH_ERR_INVALID;
   const CsvFiles f{csv, csv_len, n_files, schema, rs->tiers, nullptr};
+  return rowset_add_chunk(rs, nullptr, nullptr, nullptr, nullptr, 0, &f, err, errlen);
+}
+
+int s3imph_rowset_add_csv_gz(s3imph_rowset* rs, const uint8_t* const* gz, const uint64_t* gz_len, uint64_t n_files,
+                             const s3imph_csv_schema* schema, uint64_t group_bytes, char* err, size_t errlen) {
+  if (!rs || !schema || (n_files && (!gz || !gz_len)) || schema->key_col < 0 || schema->size_col < 0)
+    return S3IMPH_ERR_INVALID;
+  for (uint64_t i = 0; i < n_files; ++i)
+    if (gz_len[i] && !gz[i]) return S3IMPH_ERR_INVALID;
+  const CsvFiles f{gz, gz_len, n_files, schema, rs->tiers, nullptr, true, group_bytes};
   return rowset_add_chunk(rs, nullptr, nullptr, nullptr, nullptr, 0, &f, err, errlen);
 }
 

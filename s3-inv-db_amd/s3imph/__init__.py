@@ -17,7 +17,8 @@ of the pipeline: ``aggregate`` (extsort.Aggregator + SortPrefixRows: object list
 rows) and ``build_index_from_objects`` (object listing -> index directory), both for a
 byte-sorted listing; ``sort_objects`` and ``build_index_from_unsorted_objects`` take one in any
 order (the stable byte-order sort and the gather run on the GPU too); ``parse_inventory_csv`` and
-``build_index_from_inventory_csv`` start from the inventory's CSV text.  With one tier id
+``build_index_from_inventory_csv`` start from the inventory's CSV text, ``gunzip`` and
+``build_index_from_inventory_csv_gz`` from the ``.csv.gz`` files (inflated on the GPU).  With one tier id
 per object (``TIERS``, ``tier_from_s3``) both also carry the per-storage-class statistics that
 ``Index.tier_breakdown*`` answer from, and ``PriceTable`` / ``Index.monthly_cost*`` price them
 (pricing.ComputeMonthlyCost per position, on the GPU); ``Index.descendants_top`` keeps the k
@@ -100,7 +101,10 @@ EXPORTS = (
     "s3imph_index_open_flags", "s3imph_index_attach_prefixes", "s3imph_index_has_prefixes",
     "s3imph_index_prefixes_plan", "s3imph_index_prefixes_fill", "s3imph_index_lookup_verify_device",
     "s3imph_index_verify_device",
+    "s3imph_gunzip_geometry", "s3imph_gunzip_room_hint", "s3imph_gunzip_device", "s3imph_gunzip_host",
+    "s3imph_index_from_csv_gz_host", "s3imph_rowset_add_csv_gz",
 )
+GZ_OK, GZ_MORE, GZ_EOF, GZ_HEADER, GZ_DATA, GZ_CHECKSUM = range(6)  # S3IMPH_GZ_*
 OPEN_PREFIXES = 1  # S3IMPH_OPEN_PREFIXES
 MERGE_MAX_RUNS = 64  # S3IMPH_MERGE_MAX_RUNS
 NUM_TIERS = 12  # S3IMPH_NUM_TIERS
@@ -190,6 +194,17 @@ class CsvInfo(ctypes.Structure):
     _fields_ = [
         ("n_records", ctypes.c_uint64), ("n_objects", ctypes.c_uint64), ("key_bytes", ctypes.c_uint64),
         ("n_short", ctypes.c_uint64), ("n_empty_key", ctypes.c_uint64), ("n_bad_size", ctypes.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
+class GunzipInfo(ctypes.Structure):
+    """s3imph_gunzip_info: how one gzip file ended (include/s3imph.h, section 5j)."""
+    _fields_ = [
+        ("out_bytes", ctypes.c_uint64), ("in_used", ctypes.c_uint64), ("members", ctypes.c_uint32),
+        ("status", ctypes.c_uint32), ("crc32", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
     ]
 
     def as_dict(self) -> dict:
@@ -347,6 +362,13 @@ def _load():
         "s3imph_rowset_add_objects": (i32, [vp, vp, vp, vp, vp, u64, cp, sz]),
         "s3imph_rowset_add_csv": (i32, [vp, P(vp), P(u64), u64, P(CsvSchema), cp, sz]),
         "s3imph_rowset_add_rows": (i32, [vp, P(RowRun), cp, sz]),
+        "s3imph_rowset_add_csv_gz": (i32, [vp, P(vp), P(u64), u64, P(CsvSchema), u64, cp, sz]),
+        "s3imph_gunzip_geometry": (None, [P(ctypes.c_uint32), P(ctypes.c_uint32), P(ctypes.c_uint32)]),
+        "s3imph_gunzip_room_hint": (u64, [vp, u64]),
+        "s3imph_gunzip_device": (i32, [vp, vp, P(u64), u64, vp, P(u64), P(GunzipInfo), vp]),
+        "s3imph_gunzip_host": (i32, [i32, P(vp), P(u64), u64, P(vp), P(u64), P(GunzipInfo), cp, sz]),
+        "s3imph_index_from_csv_gz_host": (i32, [i32, P(vp), P(u64), u64, P(CsvSchema), i32, ctypes.c_uint32, u64, cp,
+                                                P(CsvInfo), cp, sz]),
         "s3imph_rowset_runs": (u64, [vp]),
         "s3imph_rowset_rows": (u64, [vp]),
         "s3imph_rowset_build": (i32, [vp, cp, cp, sz]),
@@ -1000,6 +1022,22 @@ class DeviceBuilder:
         return {"keys": keys[: (end + 7) // 8 * 8] if d_keys is None else keys, "offsets": offs[: n + 1],
                 "sizes": sizes[:n], "tiers": None if tiers is None else tiers[:n], "key_bytes": info["key_bytes"]}
 
+    def gunzip(self, d_gz, gz_offsets, d_out, out_offsets, stream=None) -> list:
+        """s3imph_gunzip_device: gzip files in HBM inflated in one launch.  File i is
+        d_gz[gz_offsets[i]:gz_offsets[i + 1]] (a uint8 tensor or an address, any alignment) and
+        may write only d_out[out_offsets[i]:out_offsets[i + 1]]; the offsets are host sequences of
+        n + 1 entries.  Returns one s3imph_gunzip_info dict per file; "status" is a GZ_* value."""
+        n = len(gz_offsets) - 1
+        if n != len(out_offsets) - 1 or n < 0:
+            raise MPHFError(ERR_INVALID, "gzip: gz_offsets and out_offsets need n + 1 entries each")
+        go = (ctypes.c_uint64 * (n + 1))(*[int(v) for v in gz_offsets])
+        oo = (ctypes.c_uint64 * (n + 1))(*[int(v) for v in out_offsets])
+        info = (GunzipInfo * max(n, 1))()
+        rc = LIB.s3imph_gunzip_device(self._h, _dev_ptr(d_gz), go, n, _dev_ptr(d_out), oo, info, _stream_ptr(stream))
+        if rc != OK:
+            raise MPHFError(rc, self.last_error() or f"gzip: {status_string(rc)}")
+        return [info[i].as_dict() for i in range(n)]
+
     def merge_rows_plan(self, d_blob, d_offsets, d_depth, d_count, d_bytes, run_starts, d_tier_count=None,
                         d_tier_bytes=None, tier_stride: int = 0, stream=None) -> dict:
         """s3imph_merge_rows_plan_device: MergeIterator (merger.go:104-140) over one row set in HBM
@@ -1252,6 +1290,65 @@ def build_index_from_inventory_csv(files, schema, out_dir: str, with_tiers: bool
     return info.as_dict()
 
 
+def _host_files(files):
+    bufs = [np.frombuffer(bytes(f), np.uint8) if not isinstance(f, np.ndarray) else np.ascontiguousarray(f, np.uint8)
+            for f in files]
+    k = len(bufs)
+    ptrs = (ctypes.c_void_p * max(k, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    lens = (ctypes.c_uint64 * max(k, 1))(*[b.size for b in bufs])
+    return bufs, ptrs, lens, k
+
+
+def gunzip_geometry() -> tuple[int, int, int]:
+    """(in_chunk_bytes, batch_symbols, waves_per_cu) of the GPU inflate (s3imph_gunzip_geometry;
+    for tests that place events on the edges)."""
+    a, b, c = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    LIB.s3imph_gunzip_geometry(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+    return a.value, b.value, c.value
+
+
+def gunzip_room_hint(data) -> int:
+    """s3imph_gunzip_room_hint (host only): min(ISIZE of the file's last four bytes,
+    1032 * len + 64), 0 for a file shorter than 18 bytes."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    return int(LIB.s3imph_gunzip_room_hint(_np_ptr(buf), len(buf)))
+
+
+def gunzip(files, device: int = 0, with_info: bool = False):
+    """s3imph_gunzip_host: gzip files (a list of bytes-likes) inflated on the GPU, one wave per
+    file -> a list of bytes; with_info also the s3imph_gunzip_info dicts.  A bad file raises
+    MPHFError(ERR_FORMAT, "gzip: file <i>: ...")."""
+    bufs, ptrs, lens, k = _host_files(files)
+    outs = (ctypes.c_void_p * max(k, 1))()
+    out_len = (ctypes.c_uint64 * max(k, 1))()
+    info = (GunzipInfo * max(k, 1))()
+    err = ctypes.create_string_buffer(1024)
+    rc = LIB.s3imph_gunzip_host(device, ptrs, lens, k, outs, out_len, info, err, 1024)
+    try:
+        _check(rc, err)
+        texts = [ctypes.string_at(outs[i], out_len[i]) if out_len[i] else b"" for i in range(k)]
+    finally:
+        for i in range(k):
+            if outs[i]:
+                LIB.s3imph_free(outs[i])
+    return (texts, [info[i].as_dict() for i in range(k)]) if with_info else texts
+
+
+def build_index_from_inventory_csv_gz(files, schema, out_dir: str, with_tiers: bool = False, max_depth: int = 0,
+                                      group_bytes: int = 0, device: int = 0) -> dict:
+    """s3imph_index_from_csv_gz_host: .csv.gz inventory files (a list of bytes-likes) -> index
+    directory.  The compressed bytes go to the GPU, which inflates them in groups of about
+    group_bytes (0: the library's default) and parses the texts where they lie; from there as
+    build_index_from_inventory_csv.  Returns the summed s3imph_csv_info."""
+    bufs, ptrs, lens, k = _host_files(files)
+    info = CsvInfo()
+    err = ctypes.create_string_buffer(1024)
+    _check(LIB.s3imph_index_from_csv_gz_host(device, ptrs, lens, k, ctypes.byref(_csv_schema(schema)),
+                                             int(with_tiers), max_depth, group_bytes, os.fsencode(out_dir),
+                                             ctypes.byref(info), err, 1024), err)
+    return info.as_dict()
+
+
 def merge_geometry() -> int:
     """The row merge's sample step (s3imph_merge_geometry): every step-th row of a run is a
     splitter; for tests that place run lengths on its edges."""
@@ -1375,6 +1472,13 @@ class RowSet:
         lens = (ctypes.c_uint64 * max(k, 1))(*[b.size for b in bufs])
         err = ctypes.create_string_buffer(1024)
         _check(LIB.s3imph_rowset_add_csv(self._h, ptrs, lens, k, ctypes.byref(_csv_schema(schema)), err, 1024), err)
+
+    def add_csv_gz(self, files, schema, group_bytes: int = 0) -> None:
+        """.csv.gz inventory files (a list of bytes-likes), inflated and parsed on the GPU: one run."""
+        bufs, ptrs, lens, k = _host_files(files)
+        err = ctypes.create_string_buffer(1024)
+        _check(LIB.s3imph_rowset_add_csv_gz(self._h, ptrs, lens, k, ctypes.byref(_csv_schema(schema)), group_bytes,
+                                            err, 1024), err)
 
     def add_rows(self, run) -> None:
         """A caller's sorted run (a tuple as merge_rows takes them), copied."""
