@@ -1,8 +1,9 @@
 // s3imph_inflate.h — the serial parts of the gzip reader (include/s3imph.h, section 5j), written
 // once for the device and the host: the CRC-32 operators, the bit reader, the Huffman table
 // builder, the gzip header walk and the decode step of RFC 1951 / RFC 1952.  s3imph_inflate.hip
-// runs them on one lane of a wave (the builder on sixteen); a stand-alone host program can drive
-// the same functions when a stream decodes wrongly.  Not part of the ABI.
+// runs them on one lane of a wave (the builder on sixteen); tools/inflate_host.cpp drives the same
+// functions on the host, for tests/test_inflate_host.py and when a stream decodes wrongly.  Not
+// part of the ABI.
 #pragma once
 
 #include <stdint.h>
@@ -55,8 +56,11 @@ S3I_HD uint32_t crc_concat(uint32_t crc_a, uint32_t crc_b, uint32_t xpow_b) { re
 // ---------------------------------------------------------------- bit reader
 // Reads a file through a window of its bytes: win[0] is file byte `base`, the window ends at file
 // byte `lim` (<= len).  No byte outside [base, lim) is ever read; bits wanted past the window come
-// as zeros and set `over`.  Callers keep br_ready() true before every step, so `over` means that
-// the file itself has ended.
+// as zeros and are counted in `zn`.  Callers keep br_ready() true before every step, so such bits
+// lie past the file's end.  They are the last ones buffered, and looking ahead at them is free:
+// only a step that has used one, which leaves fewer bits buffered than zeros supplied, has run
+// over the end (br_over).  A corrupt symbol just before the end is therefore corrupt input, as for
+// a reader that takes bits only as it needs them, and not an unexpected EOF.
 struct BitReader {
   const uint8_t* win;
   int64_t base;
@@ -64,7 +68,7 @@ struct BitReader {
   uint64_t pos;  // next file byte to take
   uint64_t bb;   // bits taken and not yet used, the next one lowest
   uint32_t bn;
-  bool over;
+  uint32_t zn;   // zero bits supplied past the end since the reader was last emptied
 };
 
 // 16 bytes lie in the window beyond the buffered bits, or the window reaches the file's end: no
@@ -79,7 +83,7 @@ S3I_HD void br_need(BitReader& r, uint32_t n) {  // n <= 57
       b = r.win[(int64_t)r.pos - r.base];
       ++r.pos;
     } else {
-      r.over = true;
+      r.zn += 8;
     }
     r.bb |= b << r.bn;
     r.bn += 8;
@@ -91,6 +95,9 @@ S3I_HD void br_drop(BitReader& r, uint32_t n) {
   r.bn -= n;
 }
 
+// A bit that the file does not hold has been used; stays true once it is.
+S3I_HD bool br_over(const BitReader& r) { return r.zn > r.bn; }
+
 S3I_HD uint32_t br_bits(BitReader& r, uint32_t n) {  // n <= 32
   br_need(r, n);
   const uint32_t v = (uint32_t)(r.bb & ((1ull << n) - 1));
@@ -100,8 +107,9 @@ S3I_HD uint32_t br_bits(BitReader& r, uint32_t n) {  // n <= 32
 
 S3I_HD void br_align(BitReader& r) { br_drop(r, r.bn & 7); }
 
-// The file byte the next bit comes from (the reader is byte-aligned where this is asked).
-S3I_HD uint64_t br_byte_pos(const BitReader& r) { return r.pos - r.bn / 8; }
+// The file byte the next bit comes from (the reader is byte-aligned where this is asked); the
+// file's length once the reader has run over its end.
+S3I_HD uint64_t br_byte_pos(const BitReader& r) { return r.pos - (r.bn > r.zn ? (r.bn - r.zn) / 8 : 0); }
 
 // ---------------------------------------------------------------- Huffman tables
 // Canonical decoding: a primary table over the next PBITS bits answers the short codes, the
@@ -172,7 +180,8 @@ S3I_HD void huff_place(H& h, const uint8_t* lens, uint32_t n, uint32_t lane, uin
   }
 }
 
-// The next symbol, or -1 when the bits are no code of the set.  Takes up to 15 bits.
+// The next symbol, or -1 when the next 15 bits begin no code of the set; those 15 bits are then
+// taken, so that br_over() tells whether the file held them all.  Takes up to 15 bits.
 template <class H>
 S3I_HD int32_t huff_decode(const H& h, BitReader& r) {
   br_need(r, 15);
@@ -195,6 +204,7 @@ S3I_HD int32_t huff_decode(const H& h, BitReader& r) {
     }
     code <<= 1;
   }
+  br_drop(r, 15);
   return -1;
 }
 
@@ -309,16 +319,17 @@ S3I_HD void dist_code(uint32_t s, uint32_t* base, uint32_t* extra) {
 
 // One step of the file.  Termination: every step that returns kCont has taken at least one bit
 // from the reader (a header byte, a block header, a code, a trailer word), except the one step per
-// dynamic block that finds its code lengths complete, and the bits are finite: past the file's
-// end the reader sets `over` and the step that sees it ends the file.  kFlush, kStored and the
-// kBuild events take no bit, and each is followed by a step that does or by kEnd: the caller
-// empties the queue, a stored block's header is behind the reader, a build moves on to kStSyms.
+// dynamic block that finds its code lengths complete, and the bits are finite: a step that takes
+// a bit past the file's end finds br_over() true behind it and ends the file.  kFlush, kStored
+// and the kBuild events take no bit, and each is followed by a step that does or by kEnd: the
+// caller empties the queue, a stored block's header is behind the reader, a build moves on to
+// kStSyms.
 S3I_HD uint32_t step(Dec& d, BitReader& r, Tabs& t, uint32_t* q, uint32_t* nq, uint32_t qcap) {
   switch (d.st) {
     case kStHeader: {
-      if (d.hs == 0 && r.bn == 0 && r.pos >= r.len) return end_with(d, d.members ? kOk : kEof);
+      if (d.hs == 0 && r.bn <= r.zn && r.pos >= r.len) return end_with(d, d.members ? kOk : kEof);
       const uint32_t b = br_bits(r, 8);
-      if (r.over) return end_with(d, kEof);
+      if (br_over(r)) return end_with(d, kEof);
       const int h = hdr_byte(d, b);
       if (h == 2) return end_with(d, kHeader);
       if (h == 1) {
@@ -329,21 +340,19 @@ S3I_HD uint32_t step(Dec& d, BitReader& r, Tabs& t, uint32_t* q, uint32_t* nq, u
       return kCont;
     }
     case kStBlock: {
-      br_need(r, 3);
-      if (r.over) return end_with(d, kEof);
       d.bfinal = br_bits(r, 1);
       const uint32_t type = br_bits(r, 2);
+      if (br_over(r)) return end_with(d, kEof);
       if (type == 0) {
         br_align(r);
-        br_need(r, 32);
-        if (r.over) return end_with(d, kEof);
         const uint32_t len = br_bits(r, 16), nlen = br_bits(r, 16);
+        if (br_over(r)) return end_with(d, kEof);
         if ((len ^ 0xFFFFu) != nlen) return end_with(d, kData);
         const uint64_t src = br_byte_pos(r);
         if (src + len > r.len) return end_with(d, kEof);
         d.ssrc = src;
         d.slen = len;
-        r.bb = 0, r.bn = 0, r.pos = src + len;  // the caller moves the window
+        r.bb = 0, r.bn = 0, r.zn = 0, r.pos = src + len;  // the caller moves the window
         d.mout += len;
         d.fout += len;
         d.st = d.bfinal ? kStTrailer0 : kStBlock;
@@ -360,16 +369,15 @@ S3I_HD uint32_t step(Dec& d, BitReader& r, Tabs& t, uint32_t* q, uint32_t* nq, u
       return end_with(d, kData);
     }
     case kStDyn: {
-      br_need(r, 14);
-      if (r.over) return end_with(d, kEof);
       d.nlen = br_bits(r, 5) + 257;
       d.ndist = br_bits(r, 5) + 1;
       const uint32_t ncl = br_bits(r, 4) + 4;
+      if (br_over(r)) return end_with(d, kEof);
       if (d.nlen > 286 || d.ndist > 30) return end_with(d, kData);
       br_need(r, 3 * ncl);  // <= 57
-      if (r.over) return end_with(d, kEof);
       const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
       for (uint32_t i = 0; i < 19; ++i) t.cllens[order[i]] = i < ncl ? (uint8_t)br_bits(r, 3) : 0;
+      if (br_over(r)) return end_with(d, kEof);
       d.li = 0;
       d.st = kStLens;
       return kBuildCl;
@@ -382,7 +390,7 @@ S3I_HD uint32_t step(Dec& d, BitReader& r, Tabs& t, uint32_t* q, uint32_t* nq, u
         return kBuildDyn;
       }
       const int32_t s = huff_decode(t.cl, r);
-      if (r.over) return end_with(d, kEof);
+      if (br_over(r)) return end_with(d, kEof);
       if (s < 0) return end_with(d, kData);
       if (s < 16) {
         t.lens[d.li++] = (uint8_t)s;
@@ -398,7 +406,7 @@ S3I_HD uint32_t step(Dec& d, BitReader& r, Tabs& t, uint32_t* q, uint32_t* nq, u
       } else {
         rep = 11 + br_bits(r, 7);
       }
-      if (r.over) return end_with(d, kEof);
+      if (br_over(r)) return end_with(d, kEof);
       if (d.li + rep > total) return end_with(d, kData);
       for (uint32_t k = 0; k < rep; ++k) t.lens[d.li++] = (uint8_t)prev;
       return kCont;
@@ -406,7 +414,7 @@ S3I_HD uint32_t step(Dec& d, BitReader& r, Tabs& t, uint32_t* q, uint32_t* nq, u
     case kStSyms: {
       if (*nq >= qcap) return kFlush;
       const int32_t s = huff_decode(t.ll, r);
-      if (r.over) return end_with(d, kEof);
+      if (br_over(r)) return end_with(d, kEof);
       if (s < 0) return end_with(d, kData);
       if (s < 256) {
         q[(*nq)++] = (uint32_t)s;
@@ -423,11 +431,11 @@ S3I_HD uint32_t step(Dec& d, BitReader& r, Tabs& t, uint32_t* q, uint32_t* nq, u
       length_code((uint32_t)s - 257, &base, &extra);
       const uint32_t len = base + br_bits(r, extra);
       const int32_t ds = huff_decode(t.dd, r);
-      if (r.over) return end_with(d, kEof);
+      if (br_over(r)) return end_with(d, kEof);
       if (ds < 0 || ds > 29) return end_with(d, kData);
       dist_code((uint32_t)ds, &base, &extra);
       const uint32_t dist = base + br_bits(r, extra);
-      if (r.over) return end_with(d, kEof);
+      if (br_over(r)) return end_with(d, kEof);
       if (len > 258 || dist > d.mout) return end_with(d, kData);  // before the member's first byte
       q[(*nq)++] = kMatch | dist << 9 | len;
       d.mout += len;
@@ -437,13 +445,13 @@ S3I_HD uint32_t step(Dec& d, BitReader& r, Tabs& t, uint32_t* q, uint32_t* nq, u
     case kStTrailer0: {
       br_align(r);
       d.mcrc = br_bits(r, 32);
-      if (r.over) return end_with(d, kEof);
+      if (br_over(r)) return end_with(d, kEof);
       d.st = kStTrailer1;
       return kCont;
     }
     default: {  // kStTrailer1
       const uint32_t isize = br_bits(r, 32);
-      if (r.over) return end_with(d, kEof);
+      if (br_over(r)) return end_with(d, kEof);
       if (isize != (uint32_t)d.mout) return end_with(d, kChecksum);
       d.crc_file = crc_concat(d.crc_file, d.mcrc, crc_xpow8(d.mout));
       ++d.members;

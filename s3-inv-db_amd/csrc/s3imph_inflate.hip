@@ -157,7 +157,7 @@ __device__ void inflate_file(InflateShared& sh, uint32_t lane, const uint8_t* gz
   r.pos = 0;
   r.bb = 0;
   r.bn = 0;
-  r.over = false;
+  r.zn = 0;
   uint64_t opos = 0;
   load_stage(sh, lane, gz, len, 0, r);
   __syncthreads();

@@ -124,6 +124,100 @@ def any_status(tr, text):
     return True
 
 
+def symbol_pairs(base_count, ext):
+    """(symbol index, extra value) with the extra bits all zero and all one, for every symbol."""
+    return sorted({(k, v) for k in range(base_count) for v in (0, (1 << ext[k]) - 1)})
+
+
+LEN_PAIRS = [(257 + k, v) for k, v in symbol_pairs(29, G.LEXT)]  # (284, 31) is length 258 the long way
+DIST_PAIRS = symbol_pairs(30, G.DEXT)
+
+
+def every_pair():
+    """Matches that use every pair of LEN_PAIRS and of DIST_PAIRS at least once."""
+    n = max(len(LEN_PAIRS), len(DIST_PAIRS))
+    out = []
+    for i in range(n):
+        out += [("ll",) + LEN_PAIRS[i % len(LEN_PAIRS)], ("dd",) + DIST_PAIRS[i % len(DIST_PAIRS)]]
+    return out
+
+
+def has_every_pair(tr):
+    return tr.len_syms >= set(LEN_PAIRS) and (284, 31) in tr.len_syms and tr.dist_syms >= set(DIST_PAIRS)
+
+
+def dynamic_member(symbols, ll_lens, dd_lens, **kw):
+    w = G.BitWriter()
+    w.dynamic(symbols, ll_lens, dd_lens, final=True, **kw)
+    return G.member(w.done(), G.expand(symbols))
+
+
+def flushed(text, mode, piece=50):
+    """A member whose writer flushed with `mode` after every `piece` bytes, as pgzip's and Go's do."""
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    raw = b"".join(c.compress(text[i:i + piece]) + c.flush(mode) for i in range(0, len(text), piece))
+    return G.member(raw + c.flush(), text)
+
+
+# 0..12 and the three repeat symbols, four bits each: a complete code-length code for the hand-made
+# headers below
+CL_WITH_REPEATS = [4] * 13 + [0] * 3 + [4] * 3
+
+
+def hand_made_valid(add):
+    """Streams that zlib never writes and RFC 1951 allows (Go's compress/flate, pgzip and Java
+    write some of them), from BitWriter.dynamic and the raw items of BitWriter.fixed."""
+    far = list(filler(32768, 6))
+    w = G.BitWriter()
+    w.fixed(far)
+    w.fixed(every_pair(), final=True)
+    add("every_length_and_distance_symbol", G.member(w.done(), G.expand(far + every_pair())),
+        lambda tr, t: has_every_pair(tr) and tr.block_types == [1, 1])
+    # 226 codes of 8 bits and 60 of 9, 2 distance codes of 4 bits and 28 of 5: both sets complete
+    add("every_symbol_of_a_dynamic_block_286_30",
+        dynamic_member(far + every_pair(), [8] * 226 + [9] * 60, [4] * 2 + [5] * 28),
+        lambda tr, t: has_every_pair(tr) and tr.dyn_blocks == [(286, 30, 30)] and tr.block_types == [2])
+    add("dynamic_smallest", dynamic_member(list(b"abbaab"), {97: 1, 98: 2, 256: 2}, [0]),
+        lambda tr, t: tr.dyn_blocks == [(257, 1, 0)] and tr.matches == 0 and t == b"abbaab")
+    add("single_distance_code",
+        dynamic_member([97, (3, 1), 98, (258, 1), (4, 1), 97], {97: 2, 98: 2, 256: 3, 257: 3, 258: 3, 285: 3}, [1]),
+        lambda tr, t: tr.dyn_blocks == [(286, 1, 1)] and tr.matches == 3 and tr.max_dist == 1 and tr.decoded_lens["dd"] == {1})
+    # the sixteen codes 0, 10, 110, ..., thirteen ones and a zero, and two of 15 bits; each used once
+    ladder = list(range(1, 16)) + [15]
+    text = list(filler(300, 15))
+    for name, lens in (("distance_codes_to_15_bits", ladder), ("distance_codes_from_15_bits", ladder[::-1])):
+        add(name, dynamic_member(text + [(3 + k, G.DBASE[k]) for k in range(16)], [8] * 226 + [9] * 60, lens),
+            lambda tr, t: all(l in tr.decoded_lens["dd"] for l in (7, 8, 9, 10, 11, 12, 13, 14, 15))
+            and {d for d, _ in tr.dist_syms} == set(range(16)) and tr.max_code_len == 15)
+    # a..n with 1..14 bits, end-of-block and length 3 with 15
+    lens = {97 + k: 1 + k for k in range(14)}
+    lens.update({256: 15, 257: 15})
+    add("literal_codes_at_every_length", dynamic_member(list(b"abcdefghijklmn") * 2 + [(3, 1)] + list(b"nmlkjihg"), lens, [1]),
+        lambda tr, t: all(l in tr.decoded_lens["ll"] for l in (10, 11, 12, 13, 14, 15)) and tr.decoded_lens["ll"] == set(range(1, 16)))
+    for name, mode in (("sync_flush_every_50_bytes", zlib.Z_SYNC_FLUSH), ("full_flush_every_50_bytes", zlib.Z_FULL_FLUSH)):
+        add(name, flushed(filler(1100, 16), mode), lambda tr, t: len(tr.block_types) >= 20 and tr.empty_stored_not_final >= 10)
+    for n in (BATCH - 1, BATCH, BATCH + 1):
+        first = list(filler(n - 2, 17)) + [(5, 9), (258, 1)]
+        second = list(b"abab") + [(4, 2)]
+        w = G.BitWriter()
+        w.fixed(first)
+        w.dynamic(second, {97: 2, 98: 2, 256: 2, 258: 2}, [0, 1])
+        w.dynamic(second, {97: 2, 98: 2, 256: 2, 258: 2}, [0, 1], final=True)
+        add("block_of_%d_symbols_then_a_dynamic_block" % n, G.member(w.done(), G.expand(first + second + second)),
+            lambda tr, t, n=n: tr.block_syms == [n, 5, 5] and tr.block_types == [1, 2, 2])
+    a, b = filler(5000, 18), filler(700, 19)
+    mid = [(258, 4000), (100, 4358), 33, (3, 4000), (258, 5000)]
+    w = G.BitWriter()
+    w.stored(a)
+    w.fixed(mid)
+    w.stored(b, final=True)
+    add("stored_then_matches_then_stored", G.member(w.done(), a + G.expand(mid, a) + b),
+        lambda tr, t: tr.block_types == [0, 1, 0] and tr.stored_lens == [5000, 700] and tr.max_dist == 5000
+        and tr.cross_block_match and IN_CHUNK * 2 < 5000)
+    for n in (8191, 8192, 8193, 16384):  # the CRC kernels cut a text every 8192 bytes
+        add("text_of_%d_bytes" % n, gz(filler(n, 20)), lambda tr, t, n=n: len(t) == n)
+
+
 def valid_cases():
     out = []
 
@@ -190,6 +284,7 @@ def valid_cases():
     cut = rows.index(b"\n", 1000) - 7
     add("record_cut_by_the_member_boundary", gz(rows[:cut]) + gz(rows[cut:]),
         lambda tr, t: tr.members == 2 and t == rows and rows[cut - 1] != 10)
+    hand_made_valid(add)
     return out
 
 
@@ -248,7 +343,90 @@ def invalid_cases():
     st = bytearray(G.member(w.done(), text))
     st[10 + 5 + 200] ^= 0x10
     add("stored_payload_bit", bytes(st), G.CHECKSUM)
+    corrupt_blocks(add)
+    cuts(add)
     return out
+
+
+def corrupt_blocks(add):
+    """The ways a Huffman block can be corrupt, each a whole member with its trailer behind it,
+    and four of them once more with the file ending right behind the bad symbol: a reader that
+    looks ahead must still call them corrupt, not cut.  zlib refuses them all."""
+    ok_ll, ok_dd = {97: 1, 256: 2, 257: 2}, [1]
+
+    def dyn(name, symbols, ll_lens, dd_lens, **kw):
+        w = G.BitWriter()
+        w.dynamic(symbols, ll_lens, dd_lens, final=True, **kw)
+        add(name, G.member(w.done(), b""), G.DATA)
+
+    def lens(name, items, tail=True):
+        w = G.BitWriter()
+        w.dynamic_header(257, 1, CL_WITH_REPEATS, items, final=True)
+        add(name, G.member(w.done(), b"") if tail else G.member(w.done(), b"")[:-8], G.DATA)
+
+    def fixed(name, symbols, tail=True):
+        w = G.BitWriter()
+        w.fixed(symbols, final=True, end=tail)
+        add(name, G.member(w.done(), b"") if tail else G.member(w.done(), b"")[:-8], G.DATA)
+
+    for n in (287, 288):
+        dyn("hlit_%d" % n, [97], ok_ll, ok_dd, hlit=n)
+    for n in (31, 32):
+        dyn("hdist_%d" % n, [97], ok_ll, ok_dd, hdist=n)
+    for sym in (286, 287):
+        fixed("fixed_symbol_%d" % sym, [65, ("ll", sym, 0)])
+    for sym in (30, 31):
+        fixed("fixed_distance_code_%d" % sym, [65, ("ll", 257, 0), ("dd", sym, 0)])
+    lens("repeat_16_first", [(16, 0)] + [(0, 0)] * 255)
+    # 258 lengths in all: 138 + 111 zeros, then a run that ends at 259
+    lens("repeat_16_one_past_the_total", [(18, 127), (18, 100), (2, 0), (2, 0), (2, 0), (2, 0), (16, 3)])
+    lens("repeat_17_one_past_the_total", [(18, 127), (18, 100), (17, 7)])
+    lens("repeat_18_one_past_the_total", [(18, 127), (18, 99), (18, 0)])
+    dyn("no_end_of_block_code", [97], {97: 1, 98: 1}, ok_dd)
+    dyn("two_literal_codes_of_length_2", [97], {97: 2, 256: 2}, ok_dd)
+    dyn("over_subscribed_literal_set", [97], {97: 1, 98: 1, 256: 1}, ok_dd)
+    dyn("over_subscribed_distance_set", [97], ok_ll, [1, 1, 1])
+    dyn("two_distance_codes_of_length_2", [97], ok_ll, [2, 2])
+    dyn("single_distance_code_of_length_2", [97], ok_ll, [2])
+    dyn("unused_bit_of_the_single_distance_code", [97, ("ll", 257, 0), ("bits", 1, 1)], ok_ll, [1])
+    dyn("match_with_an_empty_distance_set", [97, ("ll", 257, 0)], ok_ll, [0])
+    w = G.BitWriter()
+    w.dynamic_header(257, 1, [0] * 19, [], final=True)
+    add("all_zero_code_length_set", G.member(w.done(), b""), G.DATA)
+    fixed("fixed_symbol_286_then_the_end", [65, ("ll", 286, 0)], tail=False)
+    fixed("distance_past_the_member_start_then_the_end", [65, ("ll", 257, 0), ("dd", 1, 0)], tail=False)
+    fixed("fixed_distance_code_30_then_the_end", [65, ("ll", 257, 0), ("dd", 30, 0)], tail=False)
+    lens("repeat_16_first_then_the_end", [(16, 0)], tail=False)
+
+
+def cuts(add):
+    """Files cut where the input stage, a dynamic header, a trailer, a stored payload or a second
+    member's header is under the reader: all unexpected EOF, and a mistake is a hang."""
+    def cut(name, data, at):
+        for n in at:
+            assert n < len(data)
+            add("%s_cut_at_%d" % (name, n), data[:n], G.EOF)
+
+    one = with_size(IN_CHUNK + 60, 81)
+    cut("one_stage", one, range(IN_CHUNK - 24, IN_CHUNK + 60))
+    two = with_size(2 * IN_CHUNK + 30, 82)
+    cut("two_stages", two, range(2 * IN_CHUNK - 24, 2 * IN_CHUNK + 30))
+    text = filler(2000, 21)
+    whole = gz(text)
+    tr = G.gunzip(whole)[1]
+    assert tr.block_types == [2]
+    bit0, bit1 = tr.dyn_headers[0]
+    cut("dynamic_header", whole, range(bit0 // 8, (bit1 + 7) // 8 + 1))
+    cut("trailer", whole, range(len(whole) - 8, len(whole)))
+    w = G.BitWriter()
+    payload = filler(IN_CHUNK + 500, 22)
+    w.stored(payload, final=True)
+    cut("stored_payload", G.member(w.done(), payload), (IN_CHUNK - 1, IN_CHUNK, IN_CHUNK + 1))
+    first = gz(filler(900, 8))
+    second = gz(filler(1300, 10), flg=2 | 4 | 8 | 16, extra=b"extra", name=b"n.csv", comment=b"c c")
+    hdr = 10 + 2 + 5 + 6 + 4 + 2
+    assert G.gunzip(first + second)[1].status == G.OK and second[hdr - 2:hdr] != second[hdr:hdr + 2]
+    cut("second_header", first + second, range(len(first) + 1, len(first) + hdr + 1))
 
 
 VALID = valid_cases()

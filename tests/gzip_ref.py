@@ -1,8 +1,8 @@
 """A pure-Python gzip reader written from RFC 1951 and RFC 1952, as section 5j of include/s3imph.h
 states the contract: the reference the GPU inflate is compared with, itself checked against zlib
 and gzip (test_gzip_ref.py).  It returns the text and a trace of what the stream held, so that a
-test case can prove that it reaches the edge it is meant for.  Beside it a tiny writer of stored
-and fixed-Huffman blocks for hand-made streams."""
+test case can prove that it reaches the edge it is meant for.  Beside it a tiny writer of stored,
+fixed-Huffman and dynamic-Huffman blocks for hand-made streams, the ones no compressor writes."""
 import struct
 import zlib
 
@@ -42,6 +42,13 @@ class Trace:
         self.crc32 = 0
         self.cross_boundary_repeat = False  # a 16/17/18 run over the literal/length - distance boundary
         self.cross_block_match = False      # a match whose source lies in an earlier block
+        self.len_syms = set()      # (length symbol, value of its extra bits) of every match
+        self.dist_syms = set()     # (distance symbol, value of its extra bits) of every match
+        self.decoded_lens = {"cl": set(), "ll": set(), "dd": set()}  # the code lengths met while decoding, per table
+        self.dyn_blocks = []       # (nlen, ndist, non-zero distance lengths) of every dynamic block
+        self.dyn_headers = []      # (first bit, bit behind the last code length) of every dynamic block, in the file
+        self.block_syms = []       # literals and matches of every block (0 for a stored one)
+        self.empty_stored_not_final = 0  # stored blocks with LEN = 0 that were not final: sync and full flushes
 
 
 class Bits:
@@ -65,6 +72,9 @@ class Bits:
 
     def byte_pos(self):
         return self.pos - self.bn // 8
+
+    def bit_pos(self):
+        return 8 * self.pos - self.bn
 
 
 def make_code(lens):
@@ -94,11 +104,12 @@ def make_code(lens):
     return table
 
 
-def decode(bits, table):
+def decode(bits, table, seen):
     code = 0
     for l in range(1, 16):
         code = code << 1 | bits.take(1)
         if (l, code) in table:
+            seen.add(l)
             return table[(l, code)]
     raise Stop(DATA)
 
@@ -106,8 +117,10 @@ def decode(bits, table):
 def inflate_member(bits, out, tr):
     start = len(out)
     while True:
+        bit0 = bits.bit_pos()
         bfinal, btype = bits.take(1), bits.take(2)
         tr.block_types.append(btype)
+        tr.block_syms.append(0)
         block_start = len(out)
         if btype == 0:
             bits.align()
@@ -120,6 +133,7 @@ def inflate_member(bits, out, tr):
             out += bits.d[p:p + ln]
             bits.pos, bits.bb, bits.bn = p + ln, 0, 0
             tr.stored_lens.append(ln)
+            tr.empty_stored_not_final += ln == 0 and not bfinal
         elif btype == 3:
             raise Stop(DATA)
         else:
@@ -135,7 +149,7 @@ def inflate_member(bits, out, tr):
                 clt = make_code(cl)
                 lens = []
                 while len(lens) < nlen + ndist:
-                    s = decode(bits, clt)
+                    s = decode(bits, clt, tr.decoded_lens["cl"])
                     if s < 16:
                         lens.append(s)
                         continue
@@ -155,24 +169,32 @@ def inflate_member(bits, out, tr):
                 if lens[256] == 0:
                     raise Stop(DATA)
                 tr.max_code_len = max(tr.max_code_len, max(lens))
+                tr.dyn_blocks.append((nlen, ndist, sum(l != 0 for l in lens[nlen:])))
+                tr.dyn_headers.append((bit0, bits.bit_pos()))
                 ll, dd = make_code(lens[:nlen]), make_code(lens[nlen:])
             while True:
-                s = decode(bits, ll)
+                s = decode(bits, ll, tr.decoded_lens["ll"])
                 if s < 256:
                     out.append(s)
+                    tr.block_syms[-1] += 1
                 elif s == 256:
                     break
                 else:
                     if s > 285:
                         raise Stop(DATA)
-                    ln = LBASE[s - 257] + bits.take(LEXT[s - 257])
-                    ds = decode(bits, dd)
+                    lx = bits.take(LEXT[s - 257])
+                    ln = LBASE[s - 257] + lx
+                    ds = decode(bits, dd, tr.decoded_lens["dd"])
                     if ds > 29:
                         raise Stop(DATA)
-                    dist = DBASE[ds] + bits.take(DEXT[ds])
+                    dx = bits.take(DEXT[ds])
+                    dist = DBASE[ds] + dx
                     if dist > len(out) - start:
                         raise Stop(DATA)
                     tr.matches += 1
+                    tr.block_syms[-1] += 1
+                    tr.len_syms.add((s, lx))
+                    tr.dist_syms.add((ds, dx))
                     tr.max_dist, tr.min_dist, tr.max_len = max(tr.max_dist, dist), min(tr.min_dist, dist), max(tr.max_len, ln)
                     tr.overlaps += dist < ln
                     if len(out) - dist < block_start:
@@ -273,32 +295,68 @@ class BitWriter:
         self.out += struct.pack("<HH", len(payload), (len(payload) ^ 0xFFFF) if nlen is None else nlen)
         self.out += payload
 
-    def fixed(self, symbols, final=False):
-        """symbols: ints (literals) and (length, distance) pairs, as one fixed-Huffman block."""
+    def fixed(self, symbols, final=False, end=True):
+        """One fixed-Huffman block of `symbols` (see _symbols); end=False leaves the end-of-block
+        code out, for a stream that is cut behind a symbol."""
         self.put(int(final), 1)
         self.put(1, 2)
+        self._symbols(symbols, canonical(FIXED_LL), canonical(FIXED_DD), end)
+
+    def dynamic(self, symbols, ll_lens, dd_lens, final=False, hlit=None, hdist=None, end=True):
+        """One dynamic-Huffman block of `symbols` (see _symbols) with the canonical codes of the
+        code lengths ll_lens and dd_lens (lists, or {symbol: length}), whatever they are: an
+        incomplete or over-subscribed set is written as it stands.  The lengths are sent with the
+        plainest code-length code, 0..15 at four bits each and HCLEN = 19, without repeats.  hlit
+        and hdist are the counts the header states when they are not the lists' lengths (the
+        refused 287, 288, 31 and 32 among them).  The end-of-block code follows where it has a
+        length and `end` is true."""
+        ll_lens, dd_lens = as_lens(ll_lens, 257), as_lens(dd_lens, 1)
+        self.dynamic_header(len(ll_lens) if hlit is None else hlit, len(dd_lens) if hdist is None else hdist,
+                            [4] * 16 + [0] * 3, [(l, 0) for l in ll_lens + dd_lens], final)
+        self._symbols(symbols, canonical(ll_lens), canonical(dd_lens), end and ll_lens[256] != 0)
+
+    def dynamic_header(self, nlen, ndist, cl_lens, cl_items, final=False):
+        """A dynamic block up to its code lengths: the counts as stated, the nineteen lengths of
+        the code-length code, then cl_items, (symbol 0..18, value of its extra bits) each."""
+        self.put(int(final), 1)
+        self.put(2, 2)
+        self.put(nlen - 257, 5)
+        self.put(ndist - 1, 5)
+        self.put(15, 4)
+        for s in CL_ORDER:
+            self.put(cl_lens[s], 3)
+        code = canonical(cl_lens)
+        for s, extra in cl_items:
+            self.put_code(*code[s])
+            self.put(extra, {16: 2, 17: 3, 18: 7}.get(s, 0))
+
+    def _symbols(self, symbols, ll, dd, end):
+        """ints are literals; (length, distance) is a match with the usual symbols; ("ll", symbol,
+        extra) and ("dd", symbol, extra) write that very symbol of the literal/length or the
+        distance code and the given value of its extra bits, so that a test picks the symbol and
+        not the value (258 as symbol 284 + 31, the refused 286, 287, 30 and 31, which have no
+        extra bits); ("bits", value, n) writes n raw bits."""
         for s in symbols:
             if isinstance(s, int):
-                self._ll(s)
+                self.put_code(*ll[s])
+            elif s[0] == "ll":
+                self.put_code(*ll[s[1]])
+                self.put(s[2], LEXT[s[1] - 257] if 257 <= s[1] <= 285 else 0)
+            elif s[0] == "dd":
+                self.put_code(*dd[s[1]])
+                self.put(s[2], DEXT[s[1]] if s[1] <= 29 else 0)
+            elif s[0] == "bits":
+                self.put(s[1], s[2])
             else:
                 ln, dist = s
                 i = max(k for k in range(29) if LBASE[k] <= ln and (k == 28 or ln != 258))
-                self._ll(257 + i)
+                self.put_code(*ll[257 + i])
                 self.put(ln - LBASE[i], LEXT[i])
                 j = max(k for k in range(30) if DBASE[k] <= dist)
-                self.put_code(j, 5)
+                self.put_code(*dd[j])
                 self.put(dist - DBASE[j], DEXT[j])
-        self._ll(256)
-
-    def _ll(self, s):
-        if s < 144:
-            self.put_code(0x30 + s, 8)
-        elif s < 256:
-            self.put_code(0x190 + s - 144, 9)
-        elif s < 280:
-            self.put_code(s - 256, 7)
-        else:
-            self.put_code(0xC0 + s - 280, 8)
+        if end:
+            self.put_code(*ll[256])
 
     def raw_bits(self, v, n):
         self.put(v, n)
@@ -308,13 +366,44 @@ class BitWriter:
         return bytes(self.out)
 
 
+def as_lens(lens, least):
+    """A list of code lengths from a list or from {symbol: length}, no shorter than `least`."""
+    if isinstance(lens, dict):
+        lens = [lens.get(s, 0) for s in range(max(lens) + 1)]
+    return list(lens) + [0] * (least - len(lens))
+
+
+def canonical(lens):
+    """{symbol: (code, length)} by RFC 1951 3.2.2, for any set of lengths: where it is
+    over-subscribed the codes run over their length, which no reader gets to see."""
+    count = [0] * 16
+    for l in lens:
+        count[l] += 1
+    count[0] = 0
+    code, nxt = 0, [0] * 16
+    for l in range(1, 16):
+        code = (code + count[l - 1]) << 1
+        nxt[l] = code
+    out = {}
+    for s, l in enumerate(lens):
+        if l:
+            out[s] = (nxt[l], l)
+            nxt[l] += 1
+    return out
+
+
 def expand(symbols, before=b""):
-    """What a run of literals and (length, distance) pairs decodes to after `before`."""
-    out = bytearray(before)
+    """What a run of BitWriter._symbols items decodes to after `before`."""
+    out, ln = bytearray(before), 0
     for s in symbols:
-        if isinstance(s, int):
-            out.append(s)
-        else:
+        if isinstance(s, int) or (s[0] == "ll" and s[1] < 256):
+            out.append(s if isinstance(s, int) else s[1])
+        elif s[0] == "ll":
+            ln = LBASE[s[1] - 257] + s[2] if s[1] > 256 else 0
+        elif s[0] == "dd":
+            for _ in range(ln):
+                out.append(out[-(DBASE[s[1]] + s[2])])
+        elif s[0] != "bits":
             for _ in range(s[0]):
                 out.append(out[-s[1]])
     return bytes(out[len(before):])

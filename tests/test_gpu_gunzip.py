@@ -86,7 +86,9 @@ def test_every_valid_stream_in_one_call(ctx):
 
 ROOMY = [c for c in NAMED if c.name in ("dynamic_level_6", "stored_65535", "fixed_258_at_32768", "rle", "two_members",
                                         "dependent_matches_over_a_batch_edge", "match_into_previous_stored_block",
-                                        "huffman_only_15_bits", "empty_member")]
+                                        "huffman_only_15_bits", "empty_member", "every_length_and_distance_symbol",
+                                        "sync_flush_every_50_bytes", "single_distance_code",
+                                        "stored_then_matches_then_stored")]
 
 
 @pytest.mark.parametrize("short", ["one_byte", "half", "all"])
@@ -97,6 +99,17 @@ def test_too_little_room_reports_the_size_and_keeps_what_fits(ctx, short):
     infos = inflate(ctx, ROOMY, rooms)
     # the empty member needs no room at all
     assert [i["status"] for i in infos] == [s3imph.GZ_MORE if n else s3imph.GZ_OK for n in sizes]
+
+
+def test_room_of_three_crc_chunks_beyond_the_text(ctx):
+    """Every room exceeds its text by 3 x 8192 + 5 bytes: k_crc32_chunks has lanes whose chunk lies
+    wholly behind the text, and k_crc32_fold ends on whole chunks for the texts that are a
+    multiple of 8192 and on a short one for the others."""
+    refs = K.refs()
+    sizes = [len(refs[c.name][0]) for c in NAMED]
+    assert {8191, 8192, 8193, 16384} <= set(sizes)
+    infos = inflate(ctx, NAMED, [n + 3 * 8192 + 5 for n in sizes])
+    assert [i["status"] for i in infos] == [s3imph.GZ_OK] * len(NAMED)
 
 
 def test_more_files_than_the_grid_has_waves(ctx):
@@ -114,7 +127,9 @@ def test_invalid_streams_end_with_their_status(ctx):
 
 BAD_NAMES = ("cut_at_33", "bad_magic_0", "wrong_fhcrc", "trailing_zeros", "zero_length", "block_type_3",
              "len_nlen_mismatch", "distance_past_the_member_start", "second_member_reaches_into_the_first",
-             "over_subscribed_code_lengths", "crc_bit", "isize_bit", "stored_payload_bit")
+             "over_subscribed_code_lengths", "crc_bit", "isize_bit", "stored_payload_bit",
+             "unused_bit_of_the_single_distance_code", "fixed_symbol_286_then_the_end",
+             "one_stage_cut_at_%d" % K.IN_CHUNK)
 
 
 @pytest.mark.parametrize("name", BAD_NAMES)
